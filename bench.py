@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """bench.py — BASELINE.json metric: Allreduce(SUM,double) GB/s, device-resident, 256 MiB.
 
-  python bench.py --gpus 1 --steps K --warmup W           # N = 1 (default)
+  python bench.py --gpus 1 --steps K --warmup W           # N = 1 (default): the headline figure only
+  python bench.py --gpus 1 --steps K --warmup W --full    # and everything measured beside it (below)
+  python bench.py ... --dump-outputs DIR                  # DIR/allreduce_recv.npy: the last timed step's recv
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
   python bench.py --gpus N --steps K --warmup W           # N > 1 without a launcher: bench.py starts
@@ -14,6 +16,7 @@ process loaded no HIP runtime and opened no GPU device) and exits with the child
 replace MPJRun's launch of one JVM per rank (src/runtime/starter/MPJRun.java:807-832). --dry-launch
 prints the child command instead; --launch forces the path at any N (rehearsals).
 
+N > 1 without --full times the headline engines only (as --no-variants); --full adds the phases below.
 Time budget (N > 1): --budget-s (default 300) bounds the optional phases, checked between phases on rank
 0 and agreed by every rank: the headline engines and the configs[3]/[4] parity run first, then the
 comparison variants, the end-to-end host rate and the HBM combine, each skipped once the budget is spent
@@ -23,9 +26,11 @@ comparison variants, the end-to-end host rate and the HBM combine, each skipped 
 Workloads (a "step" = one pass of the hot path over one batch of resident synthetic input):
   N = 1: the metric's own point at one GPU — mpjx_allreduce(SUM, DOUBLE) of 256 MiB on a world of one
          rank (Reduce = arraycopy send -> recv, Bcast = nothing: 2 S of HBM traffic); step i on
-         (send, recv) pair i % --sets (4), so no step reuses the Infinity Cache. BASELINE configs[1]
-         (local Op.SUM combine of two 256 MiB double[], inout[i] = in[i] + inout[i]) is reported in
-         the same line as "combine", with its own roofline and parity.
+         (send, recv) pair i % --sets (4), so no step reuses the Infinity Cache. A plain run sets up,
+         warms up, times the K steps, checks every result element and prints the line. With --full,
+         BASELINE configs[1] (local Op.SUM combine of two 256 MiB double[], inout[i] = in[i] + inout[i])
+         is reported in the same line as "combine", with its own roofline and parity, beside the
+         measured copy and read peaks, configs[0] in multicore mode and the CPU baselines.
   N > 1: BASELINE configs[2] at N ranks — Allreduce SUM double, 256 MiB per rank, one process per
          GPU. Both libmpjx engines are timed on the same buffers — the RCCL exchange engine
          (exchange -> MST-order P-way HIP combine -> all-gather) and the HIP-IPC direct engine (one
@@ -71,6 +76,16 @@ def parse(argv=None):
     ap.add_argument("--sets", type=int, default=4,
                     help="N=1: independent operand sets cycled per step (cold operands: nothing reused "
                          "from the Infinity Cache)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure. N=1: the configs[1] combine (cold and "
+                         "warm, full parity), the measured copy and read peaks, configs[0] in multicore mode and "
+                         "from native rank threads, the CPU baselines. N>1: the comparison variants, the other "
+                         "configs, the end-to-end host rate and the HBM combine. Without it only the headline "
+                         "workload is set up, warmed up, timed and checked")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (the recv vector of the "
+                         "reported Allreduce; a fixed, seeded sample where it exceeds the size limit) as "
+                         "DIR/<name>.npy, float64")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline sample budget")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-variants", action="store_true", help="N>1: skip the comparison timings")
@@ -555,6 +570,35 @@ def pick_reported(engine_names, engines):
     return min(pool, key=lambda e: engines[e]["t"]) if pool else None
 
 
+DUMP_MAX_BYTES = 32 << 20  # --dump-outputs: bytes kept of one output vector (float64)
+
+
+def dump_sample_idx(n):
+    """The elements of an n-element output that --dump-outputs keeps: None (all of them) while they fit
+    DUMP_MAX_BYTES as float64, else a fixed sample — seeded, sorted, the first and last element
+    included — the same for every run with the same n."""
+    k = DUMP_MAX_BYTES // 8
+    if n <= k:
+        return None
+    rng = np.random.default_rng(0x4D504A00)
+    return np.unique(np.concatenate([rng.integers(0, n, k - 2), [0, n - 1]]))
+
+
+def dump_take(t):
+    """What --dump-outputs keeps of the device vector t (dump_sample_idx), as a host float64 array."""
+    idx = dump_sample_idx(t.numel())
+    if idx is not None:
+        t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+    return t.detach().reshape(-1).cpu().numpy().astype(np.float64)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs DIR: one DIR/<name>.npy per array (float64)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+
+
 def traffic_from_profiles(kernel_tag):
     """HBM bytes per launch from the committed rocprofv3 PMC summary (profiles/), or None."""
     p = os.path.join(ROOT, "profiles", "traffic.json")
@@ -743,12 +787,13 @@ def configs0_native():
         return {"error": str(e)[:200]}
 
 
-def allreduce_p1(L, n, dev, steps, warmup, sets):
+def allreduce_p1(L, n, dev, steps, warmup, sets, dump=False):
     """The metric's own P = 1 point (Allreduce at one rank = 2·S of HBM traffic, read send
     + write recv): mpjx_allreduce on a world of one rank, 256 MiB double, on the communicator's own
     stream (stream argument NULL, as the JNI shim calls it), timed with HIP events on that stream
     around K back-to-back calls, step i on (send, recv) pair i % sets (cold, as the combine); every
-    result is checked bit for bit (it is a copy)."""
+    result is checked bit for bit (it is a copy). dump: "dump" holds what --dump-outputs keeps of the
+    last timed call's recv."""
     from mpjexpress_amd import _lib
 
     arr = (ctypes.c_void_p * 1)()
@@ -786,14 +831,95 @@ def allreduce_p1(L, n, dev, steps, warmup, sets):
         used = bufs[:min(sets, steps + warmup)]  # every pair a call wrote
         ok = all(bool(torch.equal(s_.view(torch.int64), r_.view(torch.int64))) for s_, r_ in used)
         S = n * 8
+        last = dump_take(bufs[(warmup + steps - 1) % sets][1]) if dump else None
         del bufs
-        return {"value": round(S / t / 1e9, 2), "unit": "GB/s", "ms_per_step": round(t * 1e3, 4),
+        return {"value": round(S / t / 1e9, 2), "unit": "GB/s", "ms_per_step": round(t * 1e3, 4), "dump": last,
                 "kernel_us": round(kern_s * 1e6, 2), "algorithmic_bytes_per_call": 2 * S, "sets": sets,
                 "hbm_GBps": round(2 * S / kern_s / 1e9, 1), "frac": round(2 * S / kern_s / 1e9 / HBM_PEAK_GBPS, 4),
                 "traffic": traffic_from_profiles("copies_256MiB"), "bit_exact": ok,
                 "kernel": "k_copies (Reduce = arraycopy send->recv, Bcast = nothing at P=1)"}
     finally:
         L.mpjx_comm_destroy(c)
+
+
+def combine_configs1(L, n, dev, steps, warmup, R):
+    """--full, N = 1 — configs[1]: inout = in + inout, 2 x 256 MiB double, one kernel per step.
+    Cold: step i works on pair i % R of R independent (inout, in) pairs, so between two uses of
+    a pair 2(R-1) x 256 MiB of other operands stream through the chip and nothing of it is left
+    in the 256 MiB Infinity Cache — every step reads its operands from HBM, as an Op.perform over
+    a freshly received message does. (Re-running the same pair lets the cache hold part of `in`
+    between steps: that warm figure is reported beside it, never as the value.)
+    Returns the line's "combine" record and the measured HBM read peak (read_peak)."""
+    from mpjexpress_amd import _lib
+
+    S = n * 8
+    stream = torch.cuda.Stream(device=dev)
+    sp = ctypes.c_void_p(stream.cuda_stream)
+    pairs = [(synth.uniform_torch(n, seed(2, 2 * k), dev), synth.uniform_torch(n, seed(2, 2 * k + 1), dev))
+             for k in range(R)]
+    uses = [0] * R
+    torch.cuda.synchronize()
+
+    def step(i):
+        io, x = pairs[i % R]
+        uses[i % R] += 1
+        _lib.check(L.mpjx_combine(MPJX_SUM, MPJX_DOUBLE, io.data_ptr(), x.data_ptr(), n, sp), "mpjx_combine")
+
+    for i in range(warmup):
+        step(i)
+    torch.cuda.synchronize()
+    # one HIP event pair on the launch stream around the K back-to-back launches: the average
+    # launch duration (incl. the ~1.5 us kernel boundary), without per-launch event packets
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    e0.record(stream)
+    for i in range(steps):
+        step(warmup + i)
+    e1.record(stream)
+    torch.cuda.synchronize()
+    t = (time.perf_counter() - t0) / steps
+    kern_s = e0.elapsed_time(e1) / steps / 1e3
+    alg = 3 * S  # read in, read inout, write inout
+    achieved = alg / kern_s / 1e9
+    # warm, for comparison only: the same pair every launch (K more launches on pair 0)
+    e0.record(stream)
+    for _ in range(steps):
+        step(0)
+    e1.record(stream)
+    torch.cuda.synchronize()
+    warm_s = e0.elapsed_time(e1) / steps / 1e3
+    traffic = traffic_from_profiles("combine_sum_f64_256MiB")
+    # full-size parity, every element of every pair: inout after its uses = in + (... + (in + inout0)),
+    # bit for bit, recomputed on the host from the same counter streams
+    bad = 0
+    full = np.arange(n, dtype=np.uint64)
+    for k in range(R):
+        got = pairs[k][0].cpu().numpy()
+        x, xin = synth.uniform_np(full, seed(2, 2 * k)), synth.uniform_np(full, seed(2, 2 * k + 1))
+        for _ in range(uses[k]):
+            np.add(xin, x, out=x)
+        bad += int(np.count_nonzero(got.view(np.uint64) != x.view(np.uint64)))
+        del got, x, xin
+    del full, pairs
+    rp = read_peak()
+    combine = {
+        "workload": "configs[1]: local Op.SUM combine of two 256 MiB double[] on 1 MI355X (kernel only, no "
+                    "RCCL); operands cold: step i on pair i % sets",
+        "value": round(S / t / 1e9, 2), "unit": "GB/s (S/t, S = 256 MiB operand)", "ms_per_step": round(t * 1e3, 4),
+        "elements": n, "bytes_per_operand": S, "op": "SUM", "datatype": "DOUBLE", "sets": R,
+        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS,
+                     "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4),
+                     "frac_of_measured_read": round(achieved / rp, 4) if rp else None,
+                     "traffic": traffic, "kernel": "k_pway<Sum<double>,2,K_FOLD,W=2,TH=1024,U=1,POL=1>",
+                     "algorithmic_bytes_per_launch": alg, "kernel_us": round(kern_s * 1e6, 2),
+                     "warm_same_buffers": {"kernel_us": round(warm_s * 1e6, 2),
+                                           "achieved": round(alg / warm_s / 1e9, 1),
+                                           "note": "the same pair every launch, for comparison only: a figure "
+                                                   "above the cold one would be Infinity-Cache reuse, not HBM"}},
+        "parity": {"elements_checked": n * R, "mismatches": bad, "bit_exact": bad == 0},
+    }
+    return combine, rp
 
 
 def main():
@@ -803,6 +929,8 @@ def main():
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if world != a.gpus:
         a.gpus = world if world > 1 else a.gpus
+    if not a.full:  # N > 1: the engines behind the headline only (the comparison phases need --full)
+        a.no_variants = True
     if a.one_device:
         local = 0
         if a.engine.startswith("rccl"):
@@ -865,83 +993,16 @@ def main():
             dist.barrier()
 
     if world == 1 and not a.allreduce:
-        # ---- configs[1]: inout = in + inout, 2 x 256 MiB double, one kernel per step ----------
-        # Cold: step i works on pair i % R of R independent (inout, in) pairs, so between two uses of
-        # a pair 2(R-1) x 256 MiB of other operands stream through the chip and nothing of it is left
-        # in the 256 MiB Infinity Cache — every step reads its operands from HBM, as an Op.perform over
-        # a freshly received message does. (Re-running the same pair lets the cache hold part of `in`
-        # between steps: that warm figure is reported beside it, never as the value.)
         R = max(2, a.sets)
-        progress("configs[1] combine")
-        stream = torch.cuda.Stream(device=dev)
-        sp = ctypes.c_void_p(stream.cuda_stream)
-        pairs = [(synth.uniform_torch(n, seed(2, 2 * k), dev), synth.uniform_torch(n, seed(2, 2 * k + 1), dev))
-                 for k in range(R)]
-        uses = [0] * R
-        torch.cuda.synchronize()
-
-        def step(i):
-            io, x = pairs[i % R]
-            uses[i % R] += 1
-            _lib.check(L.mpjx_combine(MPJX_SUM, MPJX_DOUBLE, io.data_ptr(), x.data_ptr(), n, sp), "mpjx_combine")
-
-        for i in range(a.warmup):
-            step(i)
-        torch.cuda.synchronize()
-        # one HIP event pair on the launch stream around the K back-to-back launches: the average
-        # launch duration (incl. the ~1.5 us kernel boundary), without per-launch event packets
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        e0.record(stream)
-        for i in range(a.steps):
-            step(a.warmup + i)
-        e1.record(stream)
-        torch.cuda.synchronize()
-        t = (time.perf_counter() - t0) / a.steps
-        kern_s = e0.elapsed_time(e1) / a.steps / 1e3
-        alg = 3 * S  # read in, read inout, write inout
-        achieved = alg / kern_s / 1e9
-        # warm, for comparison only: the same pair every launch (K more launches on pair 0)
-        e0.record(stream)
-        for _ in range(a.steps):
-            step(0)
-        e1.record(stream)
-        torch.cuda.synchronize()
-        warm_s = e0.elapsed_time(e1) / a.steps / 1e3
-        traffic = traffic_from_profiles("combine_sum_f64_256MiB")
-        # full-size parity, every element of every pair: inout after its uses = in + (... + (in + inout0)),
-        # bit for bit, recomputed on the host from the same counter streams
-        bad = 0
-        full = np.arange(n, dtype=np.uint64)
-        for k in range(R):
-            got = pairs[k][0].cpu().numpy()
-            x, xin = synth.uniform_np(full, seed(2, 2 * k)), synth.uniform_np(full, seed(2, 2 * k + 1))
-            for _ in range(uses[k]):
-                np.add(xin, x, out=x)
-            bad += int(np.count_nonzero(got.view(np.uint64) != x.view(np.uint64)))
-            del got, x, xin
-        del full, pairs
-        rp = read_peak()
-        combine = {
-            "workload": "configs[1]: local Op.SUM combine of two 256 MiB double[] on 1 MI355X (kernel only, no "
-                        "RCCL); operands cold: step i on pair i % sets",
-            "value": round(S / t / 1e9, 2), "unit": "GB/s (S/t, S = 256 MiB operand)", "ms_per_step": round(t * 1e3, 4),
-            "elements": n, "bytes_per_operand": S, "op": "SUM", "datatype": "DOUBLE", "sets": R,
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4),
-                         "frac_of_measured_read": round(achieved / rp, 4) if rp else None,
-                         "traffic": traffic, "kernel": "k_pway<Sum<double>,2,K_FOLD,W=2,TH=1024,U=1,POL=1>",
-                         "algorithmic_bytes_per_launch": alg, "kernel_us": round(kern_s * 1e6, 2),
-                         "warm_same_buffers": {"kernel_us": round(warm_s * 1e6, 2),
-                                               "achieved": round(alg / warm_s / 1e9, 1),
-                                               "note": "the same pair every launch, for comparison only: a figure "
-                                                       "above the cold one would be Infinity-Cache reuse, not HBM"}},
-            "parity": {"elements_checked": n * R, "mismatches": bad, "bit_exact": bad == 0},
-        }
+        combine = rp = None
+        if a.full:  # configs[1] first, then the headline, as every earlier line was measured
+            progress("configs[1] combine")
+            combine, rp = combine_configs1(L, n, dev, a.steps, a.warmup, R)
         # ---- the metric's own P = 1 point: Allreduce SUM double 256 MiB on a world of one rank ----
         progress("Allreduce at P = 1")
-        ar = allreduce_p1(L, n, dev, a.steps, a.warmup, R)
+        ar = allreduce_p1(L, n, dev, a.steps, a.warmup, R, dump=bool(a.dump_outputs))
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, {"allreduce_recv": ar["dump"]})
         out = {
             "metric": METRIC, "value": ar["value"], "unit": "GB/s", "n_gpus": 1,
             "steps": a.steps, "warmup": a.warmup, "ms_per_step": ar["ms_per_step"],
@@ -954,23 +1015,28 @@ def main():
                        "elements": n, "bytes_per_rank": S, "op": "SUM", "datatype": "DOUBLE",
                        "sets": R, "parallelism": "single GPU", "engine": "one rank (copy)"},
             "roofline": {"bound": "hbm", "achieved": ar["hbm_GBps"], "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": ar["frac"], "frac_of_measured_read": round(ar["hbm_GBps"] / rp, 4) if rp else None,
+                         "frac": ar["frac"],
                          "traffic": ar["traffic"], "kernel": "k_copies<true> (512 lanes x one 16-B vector, non-temporal)",
-                         "algorithmic_bytes_per_launch": ar["algorithmic_bytes_per_call"], "kernel_us": ar["kernel_us"],
-                         "measured_copy_GBps": copy_peak(n, dev), "measured_read_GBps": rp},
+                         "algorithmic_bytes_per_launch": ar["algorithmic_bytes_per_call"], "kernel_us": ar["kernel_us"]},
             "parity": {"elements_checked": n * R, "bit_exact": ar["bit_exact"],
                        "reference_order": "P = 1: recv = send, bit for bit"},
-            "combine": combine,
+            "full": a.full,
         }
-        progress("configs[0] in multicore mode")
-        try:
-            out["configs0_multicore_p4"] = configs0_multicore(L, dev, max(200, 10 * a.steps))
-        except Exception as e:  # noqa: BLE001  (a variant's failure must not lose the headline)
-            out["configs0_multicore_p4"] = {"error": str(e)[:200]}
-        out["configs0_multicore_p4"]["native_rank_threads"] = configs0_native()
-        if not a.no_cpu_baseline:
-            progress("cpu baseline")
-            out["cpu_baseline"] = cpu_baseline(n, a.cpu_seconds)
+        if a.dump_outputs:
+            out["dumped"] = {"allreduce_recv": int(ar["dump"].size), "of_elements": n}
+        if a.full:  # everything beside the headline figure: runs of their own
+            out["roofline"].update({"frac_of_measured_read": round(ar["hbm_GBps"] / rp, 4) if rp else None,
+                                    "measured_copy_GBps": copy_peak(n, dev), "measured_read_GBps": rp})
+            out["combine"] = combine
+            progress("configs[0] in multicore mode")
+            try:
+                out["configs0_multicore_p4"] = configs0_multicore(L, dev, max(200, 10 * a.steps))
+            except Exception as e:  # noqa: BLE001  (a variant's failure must not lose the headline)
+                out["configs0_multicore_p4"] = {"error": str(e)[:200]}
+            out["configs0_multicore_p4"]["native_rank_threads"] = configs0_native()
+            if not a.no_cpu_baseline:
+                progress("cpu baseline")
+                out["cpu_baseline"] = cpu_baseline(n, a.cpu_seconds)
         out["runtime"] = runtime_versions(L)
         print(json.dumps(out), flush=True)
         return
@@ -1235,6 +1301,7 @@ def main():
         dist.destroy_process_group()
         raise SystemExit(1)
     rcomm = None
+    dumps = {}  # rank 0, --dump-outputs: what is kept of each engine's recv after its last timed step
     for i, eng in enumerate(engine_names):
         # each engine in a world of its own, timed alone: an IPC world is destroyed before the next one
         # is created (two live worlds in the same processes slowed the second 10x). The
@@ -1255,6 +1322,8 @@ def main():
 
                 te = timed(step, a.steps, a.warmup, c)
                 mism, full = parity()
+                if a.dump_outputs and rank == 0:
+                    dumps[eng] = dump_take(recv)
                 engines[eng] = {"ms": round(te * 1e3, 4),
                                 "busbw_GBps": round(S / te / 1e9 * 2 * (world - 1) / world, 2),
                                 "mismatches": mism, "full_checksum_match": full, "t": te}
@@ -1276,6 +1345,9 @@ def main():
     if best is None:
         raise RuntimeError(f"no engine ran: {engines}")
     best_kind = "rccl" if best.startswith("rccl") else best
+    if a.dump_outputs and rank == 0 and best in dumps:  # rank 0's recv from the reported engine
+        dump_outputs(a.dump_outputs, {"allreduce_recv": dumps[best]})
+    dumps.clear()
 
     def configs_on(eng):
         """The other BASELINE configs at this N (full-size parity checked on device) on engine `eng`: the

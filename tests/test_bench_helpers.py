@@ -55,6 +55,37 @@ def test_checksum_fingerprint():
     assert bench.checksum(np.array([2 ** 63, 2 ** 63], dtype=np.uint64)) == (0, 0)  # xor cancels, sum wraps
 
 
+def test_dump_sample_is_fixed_and_bounded(tmp_path):
+    """--dump-outputs: an output that fits is kept whole; a larger one is sampled at indices that are the
+    same in every run (seeded), sorted, within DUMP_MAX_BYTES as float64, first and last included; the
+    files are float64 .npy."""
+    import torch
+
+    import bench
+
+    k = bench.DUMP_MAX_BYTES // 8
+    assert 8 * k <= 64 * 10 ** 6 and bench.dump_sample_idx(k) is None
+    n = (256 << 20) // 8
+    idx = bench.dump_sample_idx(n)
+    assert np.array_equal(idx, bench.dump_sample_idx(n))
+    assert idx[0] == 0 and idx[-1] == n - 1 and np.all(np.diff(idx) > 0) and k // 2 < idx.size <= k
+    t = torch.arange(1000, dtype=torch.float32)
+    got = bench.dump_take(t)
+    assert got.dtype == np.float64 and np.array_equal(got, np.arange(1000.0))
+    bench.dump_outputs(str(tmp_path / "d"), {"x": got})
+    back = np.load(tmp_path / "d" / "x.npy")
+    assert back.dtype == np.float64 and np.array_equal(back, got)
+
+
+def test_full_and_dump_outputs_are_off_by_default():
+    import bench
+
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    a = bench.parse(["--full", "--dump-outputs", "somewhere"])
+    assert a.full is True and a.dump_outputs == "somewhere"
+
+
 def _preflight_worker(rank, P, port, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     import torch.distributed as dist

@@ -40,6 +40,33 @@ def _engines_exact(d):
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_only_and_dumps_its_last_recv(tmp_path):
+    """A plain N = 1 run measures the headline only (nothing that --full adds is in the line), --steps
+    sets the timed steps, and --dump-outputs writes the last timed step's recv: at P = 1 the send stream
+    of pair (warmup + steps - 1) % sets, bit for bit (8 MiB: kept whole)."""
+    import numpy as np
+
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import synth
+
+    out = tmp_path / "dump"
+    d = _bench(["--gpus", "1", "--steps", "4", "--warmup", "2", "--mib", "8", "--dump-outputs", str(out)], timeout=120)
+    assert d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 2 and d["full"] is False
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["parity"]["bit_exact"] is True
+    assert d["unit"] == "GB/s" and d["dtype"] == "f64" and d["higher_is_better"] is True
+    # value = S / t and ms_per_step = t, each rounded (2 and 4 decimals): equal within those roundings
+    assert abs(d["value"] - (8 << 20) / (d["ms_per_step"] * 1e-3) / 1e9) <= d["value"] * 1e-4 / d["ms_per_step"] + 0.01
+    for k in ("combine", "cpu_baseline", "configs0_multicore_p4"):
+        assert k not in d, k
+    assert "measured_copy_GBps" not in d["roofline"]
+    assert sorted(os.listdir(out)) == ["allreduce_recv.npy"]
+    got = np.load(out / "allreduce_recv.npy")
+    n = (8 << 20) // 8
+    exp = synth.uniform_np(np.arange(n, dtype=np.uint64), synth.seed(3, (2 + 4 - 1) % d["config"]["sets"]))
+    assert got.dtype == np.float64 and np.array_equal(got.view(np.uint64), exp.view(np.uint64))
+
+
+@pytest.mark.gpu
 def test_bench_self_launched_world1_rehearsal():
     d = _bench(["--launch", "--allreduce", "--steps", "3", "--warmup", "1", "--no-variants", "--budget-s", "200"])
     assert d["n_gpus"] == 1 and d["value"] > 0 and d["parity"]["bit_exact"] is True, d.get("parity")
@@ -68,7 +95,8 @@ def test_bench_world1_rccl_native_is_a_variant_not_the_engine():
     reported engine as the comparison variant `rccl_native` (on a communicator of its own: the routing is
     read at init), never reported as the line's engine; the reported engine is one of libmpjx's
     HIP-combine engines. World-1 self-launched rehearsal with the comparison variants on."""
-    d = _bench(["--launch", "--allreduce", "--steps", "3", "--warmup", "1", "--budget-s", "300"], timeout=600)
+    d = _bench(["--launch", "--allreduce", "--full", "--steps", "3", "--warmup", "1", "--budget-s", "300"],
+               timeout=600)
     import bench
 
     assert d["config"]["engine"] in bench.HEADLINE_ENGINES and "rccl_native" not in d["engines"], d["config"]

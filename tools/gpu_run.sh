@@ -5,7 +5,7 @@
 # stops at the first failure (no GPU step runs after a fault, an abort or a time limit).
 # Steps:
 #   pytest        the whole -m gpu suite              pytest_k:EXPR   the -m gpu tests matching EXPR
-#   smoke         __graft_entry__.smoke()             bench           python bench.py (N = 1 line)
+#   smoke         __graft_entry__.smoke()             bench           python bench.py --full (N = 1 line)
 #   rocprof       rocprofv3 --kernel-trace --stats of the N = 1 bench
 #   pmc_bench     rocprofv3 --pmc FETCH_SIZE, then WRITE_SIZE, of the N = 1 bench (one counter per pass)
 #   ar1           N > 1 bench flow at world size 1 (torchrun, --allreduce: preflights, every engine)
@@ -71,29 +71,29 @@ for step in "$@"; do
             tail -2 "$OUT/${TAG}_pytest_k.log" ;;
     smoke) run smoke 300 bash -c "python -c 'import __graft_entry__ as g; g.smoke()' > '$OUT/${TAG}_smoke.log' 2>&1"
            tail -1 "$OUT/${TAG}_smoke.log" ;;
-    bench) run bench 400 bash -c "python bench.py > '$OUT/${TAG}_bench_n1.json' 2> '$OUT/${TAG}_bench_n1.err'"
+    bench) run bench 400 bash -c "python bench.py --full > '$OUT/${TAG}_bench_n1.json' 2> '$OUT/${TAG}_bench_n1.err'"
            head -c 600 "$OUT/${TAG}_bench_n1.json"; echo ;;
-    rocprof) run rocprof 400 bash -c "cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d '$OUT/${TAG}_prof' -o bench -- python3 '$R/bench.py' --no-cpu-baseline --steps 20 > '$OUT/${TAG}_rocprof.log' 2>&1" ;;
+    rocprof) run rocprof 400 bash -c "cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d '$OUT/${TAG}_prof' -o bench -- python3 '$R/bench.py' --full --no-cpu-baseline --steps 20 > '$OUT/${TAG}_rocprof.log' 2>&1" ;;
     pmc_bench)
-      run pmc_fetch 300 bash -c "cd /tmp && rocprofv3 --pmc FETCH_SIZE --output-format csv -d '$OUT/${TAG}_pmcb_fetch' -o bench -- python3 '$R/bench.py' --no-cpu-baseline --steps 5 --warmup 1 > '$OUT/${TAG}_pmcb_fetch.log' 2>&1"
-      run pmc_write 300 bash -c "cd /tmp && rocprofv3 --pmc WRITE_SIZE --output-format csv -d '$OUT/${TAG}_pmcb_write' -o bench -- python3 '$R/bench.py' --no-cpu-baseline --steps 5 --warmup 1 > '$OUT/${TAG}_pmcb_write.log' 2>&1" ;;
-    ar1) run ar1 500 bash -c "$TR --nproc-per-node 1 --master-port 29612 bench.py --allreduce --steps 10 --warmup 3 > '$OUT/${TAG}_bench_ar1.json' 2> '$OUT/${TAG}_bench_ar1.err'"
+      run pmc_fetch 300 bash -c "cd /tmp && rocprofv3 --pmc FETCH_SIZE --output-format csv -d '$OUT/${TAG}_pmcb_fetch' -o bench -- python3 '$R/bench.py' --full --no-cpu-baseline --steps 5 --warmup 1 > '$OUT/${TAG}_pmcb_fetch.log' 2>&1"
+      run pmc_write 300 bash -c "cd /tmp && rocprofv3 --pmc WRITE_SIZE --output-format csv -d '$OUT/${TAG}_pmcb_write' -o bench -- python3 '$R/bench.py' --full --no-cpu-baseline --steps 5 --warmup 1 > '$OUT/${TAG}_pmcb_write.log' 2>&1" ;;
+    ar1) run ar1 500 bash -c "$TR --nproc-per-node 1 --master-port 29612 bench.py --allreduce --full --steps 10 --warmup 3 > '$OUT/${TAG}_bench_ar1.json' 2> '$OUT/${TAG}_bench_ar1.err'"
          head -c 400 "$OUT/${TAG}_bench_ar1.json"; echo ;;
-    ar1_fail) run ar1_fail 500 bash -c "MPJX_PREFLIGHT_FAIL=rccl $TR --nproc-per-node 1 --master-port 29613 bench.py --allreduce --steps 5 --warmup 2 > '$OUT/${TAG}_bench_ar1_fail.json' 2> '$OUT/${TAG}_bench_ar1_fail.err'"
+    ar1_fail) run ar1_fail 500 bash -c "MPJX_PREFLIGHT_FAIL=rccl $TR --nproc-per-node 1 --master-port 29613 bench.py --allreduce --full --steps 5 --warmup 2 > '$OUT/${TAG}_bench_ar1_fail.json' 2> '$OUT/${TAG}_bench_ar1_fail.err'"
          head -c 400 "$OUT/${TAG}_bench_ar1_fail.json"; echo ;;
-    od4) run od4 600 bash -c "$TR --nproc-per-node 4 --master-port 29614 bench.py --gpus 4 --one-device --steps 5 --warmup 2 > '$OUT/${TAG}_bench_od4.json' 2> '$OUT/${TAG}_bench_od4.err'"
+    od4) run od4 600 bash -c "$TR --nproc-per-node 4 --master-port 29614 bench.py --gpus 4 --one-device --full --steps 5 --warmup 2 > '$OUT/${TAG}_bench_od4.json' 2> '$OUT/${TAG}_bench_od4.err'"
          head -c 400 "$OUT/${TAG}_bench_od4.json"; echo ;;
-    launch1) run launch1 500 bash -c "python bench.py --launch --allreduce --steps 10 --warmup 3 > '$OUT/${TAG}_bench_launch1.json' 2> '$OUT/${TAG}_bench_launch1.err'"
+    launch1) run launch1 500 bash -c "python bench.py --launch --allreduce --full --steps 10 --warmup 3 > '$OUT/${TAG}_bench_launch1.json' 2> '$OUT/${TAG}_bench_launch1.err'"
          head -c 400 "$OUT/${TAG}_bench_launch1.json"; echo ;;
-    launch1_budget) run launch1_budget 400 bash -c "python bench.py --launch --allreduce --steps 5 --warmup 2 --budget-s 30 > '$OUT/${TAG}_bench_launch1_budget.json' 2> '$OUT/${TAG}_bench_launch1_budget.err'"
+    launch1_budget) run launch1_budget 400 bash -c "python bench.py --launch --allreduce --full --steps 5 --warmup 2 --budget-s 30 > '$OUT/${TAG}_bench_launch1_budget.json' 2> '$OUT/${TAG}_bench_launch1_budget.err'"
          head -c 400 "$OUT/${TAG}_bench_launch1_budget.json"; echo ;;
-    launch1_budget5) run launch1_budget5 400 bash -c "python bench.py --launch --allreduce --steps 5 --warmup 2 --budget-s 5 > '$OUT/${TAG}_bench_launch1_budget5.json' 2> '$OUT/${TAG}_bench_launch1_budget5.err'"
+    launch1_budget5) run launch1_budget5 400 bash -c "python bench.py --launch --allreduce --full --steps 5 --warmup 2 --budget-s 5 > '$OUT/${TAG}_bench_launch1_budget5.json' 2> '$OUT/${TAG}_bench_launch1_budget5.err'"
          head -c 400 "$OUT/${TAG}_bench_launch1_budget5.json"; echo ;;
-    launch1_hard) run launch1_hard 400 bash -c "MPJX_BENCH_STALL_PHASE=e2e_host python bench.py --launch --allreduce --steps 5 --warmup 2 --no-preflight --hard-s 30 > '$OUT/${TAG}_bench_launch1_hard.json' 2> '$OUT/${TAG}_bench_launch1_hard.err'"
+    launch1_hard) run launch1_hard 400 bash -c "MPJX_BENCH_STALL_PHASE=e2e_host python bench.py --launch --allreduce --full --steps 5 --warmup 2 --no-preflight --hard-s 30 > '$OUT/${TAG}_bench_launch1_hard.json' 2> '$OUT/${TAG}_bench_launch1_hard.err'"
          head -c 400 "$OUT/${TAG}_bench_launch1_hard.json"; echo ;;
-    od8_launch) run od8_launch 600 bash -c "python bench.py --gpus 8 --one-device --steps 5 --warmup 2 > '$OUT/${TAG}_bench_od8_launch.json' 2> '$OUT/${TAG}_bench_od8_launch.err'"
+    od8_launch) run od8_launch 600 bash -c "python bench.py --gpus 8 --one-device --full --steps 5 --warmup 2 > '$OUT/${TAG}_bench_od8_launch.json' 2> '$OUT/${TAG}_bench_od8_launch.err'"
          head -c 400 "$OUT/${TAG}_bench_od8_launch.json"; echo ;;
-    od4_launch) run od4_launch 600 bash -c "python bench.py --gpus 4 --one-device --steps 5 --warmup 2 > '$OUT/${TAG}_bench_od4_launch.json' 2> '$OUT/${TAG}_bench_od4_launch.err'"
+    od4_launch) run od4_launch 600 bash -c "python bench.py --gpus 4 --one-device --full --steps 5 --warmup 2 > '$OUT/${TAG}_bench_od4_launch.json' 2> '$OUT/${TAG}_bench_od4_launch.err'"
          head -c 400 "$OUT/${TAG}_bench_od4_launch.json"; echo ;;
     jni_latency) run jni_latency 200 bash -c "python tests/jni_driver.py latency > '$OUT/${TAG}_jni_latency.json' 2> '$OUT/${TAG}_jni_latency.err'"
          cat "$OUT/${TAG}_jni_latency.json" ;;
