@@ -37,6 +37,57 @@ constexpr size_t kAlignBytes = 256;
 
 size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// ---- knobs read from the environment by every call ----
+
+size_t in_slot_skew() {  // MPJX_SLOT_SKEW (bytes, read per call; rounded to 256): input-slot skew (see Slots)
+  const char* e = getenv("MPJX_SLOT_SKEW");
+  const long v = e ? atol(e) : 0;
+  return v > 0 ? ((size_t)v + 255) & ~(size_t)255 : 0;
+}
+
+// Small vectors (<= MPJX_ONESHOT_KIB per rank, read per call, default 256): one all-gather of the
+// whole vectors and a local P-way combine of all of them, instead of exchange -> combine -> exchange:
+// one collective's latency instead of two. Every rank evaluates the same tree, so the bits match.
+bool oneshot(size_t bytes) {
+  const char* e = getenv("MPJX_ONESHOT_KIB");
+  const long kib = e ? atol(e) : 256;
+  return kib > 0 && bytes <= ((size_t)kib << 10);
+}
+
+// MPJX_PIPE_CHUNK_MIB (read per call): chunk size of the pipelined Allreduce; unset or 0 = off. Off by
+// default: on one GPU (configs[4], exchange engine with device copies as transport) it ran 17.8 ms at
+// 64 MiB chunks vs 7.7 ms unchunked (profiles/r02/c5_overlap.json) — every chunk adds two collectives'
+// fixed cost, and there the "links" are the same HBM the combine streams. The bench times it at N > 1,
+// where exchange #1 and the all-gather use different xGMI directions; the 8-GPU run decides.
+size_t pipe_chunk_bytes() {
+  const char* e = getenv("MPJX_PIPE_CHUNK_MIB");
+  long m = e ? atol(e) : 0;
+  return m > 0 ? (size_t)m << 20 : 0;
+}
+
+size_t host_chunk_bytes() {  // MPJX_HOST_CHUNK_MIB (read per call) overrides the pipeline granularity
+  const char* e = getenv("MPJX_HOST_CHUNK_MIB");
+  const long m = e ? atol(e) : 0;
+  return (size_t)(m > 0 ? m : 16) << 20;
+}
+
+bool smp_copy() {  // MPJX_SMP_COPY=1 forces the copy-based exchanges instead of the direct paths
+  const char* e = getenv("MPJX_SMP_COPY");
+  return e && *e && strcmp(e, "0") != 0;
+}
+
+bool host_direct_off() {  // MPJX_HOST_DIRECT=0 turns the *_host calls' host-direct form off
+  const char* e = getenv("MPJX_HOST_DIRECT");
+  return e && *e && strcmp(e, "0") == 0;
+}
+
+// The chunk pipelines' chunk: `want` bytes cut to a multiple of P x 256 B (at least one), so every
+// chunk splits into equal, aligned blocks
+size_t chunk_bytes(int P, size_t want) {
+  const size_t unit = (size_t)P * kAlignBytes;
+  return std::max(unit, want / unit * unit);
+}
+
 // Per-call context: device, stream ordering against the previous call, scratch.
 struct Call {
   mpjx_comm* c;
@@ -115,12 +166,6 @@ struct Blocks {
 // measures as the bench variant rccl_skew).
 constexpr size_t kSlotSkew = 4096;
 
-size_t in_slot_skew() {  // MPJX_SLOT_SKEW (bytes, read per call; rounded to 256): input-slot skew
-  const char* e = getenv("MPJX_SLOT_SKEW");
-  const long v = e ? atol(e) : 0;
-  return v > 0 ? ((size_t)v + 255) & ~(size_t)255 : 0;
-}
-
 struct Slots {
   char* base;
   size_t stride;   // bytes per input slot
@@ -142,6 +187,14 @@ size_t temp_bytes(int P, int64_t n, int esz) {
   int levels = 0;
   for (int m = P; m > MAXP; m = (m + 1) / 2) levels++;
   return (size_t)(2 * levels + 2) * round_up((size_t)n * esz, kAlignBytes);
+}
+
+// Scratch for the slots S, the temporaries of an n-element combine behind them (*ts) and `extra` bytes
+int carve(Call& k, Slots* S, int64_t n, TempStack* ts, size_t extra = 0) {
+  CHK(k.scratch(S->bytes() + temp_bytes(S->P, n, k.esz) + extra));
+  S->base = k.c->scratch;
+  *ts = TempStack{S->tail(), k.c->scratch_bytes - S->bytes(), 0, (size_t)k.esz};
+  return MPJX_SUCCESS;
 }
 
 // MPJX_P1_EXCHANGE=1: run world-size-1 Allreduce through the full exchange path (test knob that
@@ -266,6 +319,57 @@ int gather_all_on(Call& k, Transport* tr, hipStream_t s, char* recv, const Block
 }
 int gather_all(Call& k, char* recv, const Blocks& B) { return gather_all_on(k, k.c->tr.get(), k.s, recv, B); }
 
+// in[j] = rank j's operand of this rank's block after exchange #1: in-slot j, or `own` (the block in
+// the caller's send) where the own block was not copied into its slot
+void slot_inputs(const Slots& S, int me, bool own_in_slot, const char* own, std::vector<const void*>* in) {
+  in->resize(S.P);
+  for (int j = 0; j < S.P; j++) (*in)[j] = (j == me && !own_in_slot) ? (const void*)own : (const void*)S.in(j);
+}
+
+// The exchange engine's first half: slots and temporaries in scratch (plan), then exchange #1 and the
+// operands of this rank's block (scatter). Two steps, so a caller's phase marks go between them.
+struct Exchange {
+  Slots S;
+  TempStack ts;
+  std::vector<const void*> in;
+  // slots of slot_elems elements (B.len[0]; Reduce_scatter: its own block, and kAlignBytes `extra`)
+  int plan(Call& k, Combine& cb, const Blocks& B, int64_t slot_elems, size_t extra = 0) {
+    S = make_slots((size_t)slot_elems * k.esz, k.c->size);
+    CHK(carve(k, &S, B.len[k.c->rank], &ts, extra));
+    cb.tmp = &ts;
+    return MPJX_SUCCESS;
+  }
+  int scatter(Call& k, const char* send, const Blocks& B) {
+    bool own_in_slot = false;
+    CHK(scatter_blocks(k, send, B, S, &own_in_slot));
+    slot_inputs(S, k.c->rank, own_in_slot, send + B.off[k.c->rank] * k.esz, &in);
+    return MPJX_SUCCESS;
+  }
+};
+
+// Every block back to its rank: out-slot j -> rank j, and block j of `recv` from rank j (the second
+// exchange of the plans whose result differs per rank: FT Allreduce, faithful Reduce partials, Scan)
+int return_blocks(Call& k, const Slots& S, const Blocks& B, char* recv) {
+  const int P = k.c->size, me = k.c->rank;
+  std::vector<Xfer> sends, recvs;
+  for (int j = 0; j < P; j++) {
+    if (j == me) continue;
+    if (B.len[me] > 0) sends.push_back({j, S.out(j), (size_t)B.len[me] * k.esz});
+    if (B.len[j] > 0) recvs.push_back({j, recv + B.off[j] * k.esz, (size_t)B.len[j] * k.esz});
+  }
+  return k.c->tr->exchange(sends, recvs, k.s);
+}
+
+// A one-rank communicator's call: the copy, between the four phase marks of engine 4
+int one_rank_copy(Call& k, Combine& cb, void* recv, const void* send, int64_t n) {
+  CHK(k.mark(0, 4));
+  CHK(k.mark(1, 4));
+  CHK(cb.copy(recv, send, n));
+  CHK(k.mark(2, 4));
+  CHK(k.mark(3, 4));
+  return MPJX_SUCCESS;
+}
+
 }  // namespace
 
 namespace {
@@ -277,10 +381,7 @@ namespace {
 // forces the copy-based exchanges instead).
 Direct* smp_direct(mpjx_comm* c) {
   auto* t = dynamic_cast<Direct*>(c->tr.get());
-  if (!t || !t->direct_ok()) return nullptr;
-  const char* e = getenv("MPJX_SMP_COPY");
-  if (e && *e && strcmp(e, "0") != 0) return nullptr;
-  return t;
+  return t && t->direct_ok() && !smp_copy() ? t : nullptr;
 }
 
 int direct_temps(Call& k, int P, int64_t n, TempStack* ts, int extra = 0) {
@@ -291,6 +392,19 @@ int direct_temps(Call& k, int P, int64_t n, TempStack* ts, int extra = 0) {
 }
 
 const char* at(const void* base, int64_t elems, int esz) { return (const char*)base + elems * esz; }
+
+// The direct engines' operands from share()'s pointers: in[j] / outs[j] = rank j's send / recv at element
+// `off` (outs[j] null where rank j shared no recv: Reduce's non-roots)
+void direct_tables(const std::vector<std::vector<const void*>>& all, int64_t off, int esz,
+                   std::vector<const void*>* in, std::vector<void*>* outs) {
+  const size_t P = all.size();
+  in->resize(P);
+  outs->resize(P);
+  for (size_t j = 0; j < P; j++) {
+    (*in)[j] = at(all[j][0], off, esz);
+    (*outs)[j] = all[j][1] ? (void*)at(all[j][1], off, esz) : nullptr;
+  }
+}
 
 // The element range [*off, *off + *n) this rank computes in direct mode: its own block of the even
 // partition when the ranks sit on different devices (each GPU's CUs reduce their share), or — all
@@ -393,61 +507,23 @@ int bkt_sendbuf(Call& k, Combine& cb, char* send, int64_t total, int64_t boff, i
 
 namespace {
 
-// MPJX_PIPE_CHUNK_MIB (read per call): chunk size of the pipelined Allreduce; unset or 0 = off. Off by
-// default: on one GPU (configs[4], exchange engine with device copies as transport) it ran 17.8 ms at
-// 64 MiB chunks vs 7.7 ms unchunked (profiles/r02/c5_overlap.json) — every chunk adds two collectives'
-// fixed cost, and there the "links" are the same HBM the combine streams. The bench times it at N > 1,
-// where exchange #1 and the all-gather use different xGMI directions; the 8-GPU run decides.
-// Small vectors (<= MPJX_ONESHOT_KIB per rank, read per call, default 256): one all-gather of the
-// whole vectors and a local P-way combine of all of them, instead of exchange -> combine -> exchange:
-// one collective's latency instead of two. Every rank evaluates the same tree, so the bits match.
-bool oneshot(size_t bytes) {
-  const char* e = getenv("MPJX_ONESHOT_KIB");
-  const long kib = e ? atol(e) : 256;
-  return kib > 0 && bytes <= ((size_t)kib << 10);
+// The one-shot engines' scratch: P slots of one whole vector each (slot j = rank j's), then temporaries
+int oneshot_slots(Call& k, int64_t count, Slots* S, TempStack* ts) {
+  *S = Slots{nullptr, round_up((size_t)count * k.esz, kAlignBytes), 0, k.c->size};  // input slots only
+  return carve(k, S, count, ts);
 }
 
-// This thread is inside the host-direct form of a *_host call (its buffers are page-locked host memory
-// at the same address on the device, and the call returns complete): set by mpjx_*_host around the
-// device entry point it hands the buffers to.
-thread_local bool t_host_direct = false;
-struct HostDirectScope {
-  HostDirectScope() { t_host_direct = true; }
-  ~HostDirectScope() { t_host_direct = false; }
-};
-
-// MPJX_HOST_ONCE=1 (off by default; read per call by rank 0 alone, which decides for the call): in the
-// host-direct form of a multicore Allreduce, rank 0's one kernel writes the result into ONE host-direct
-// rank's recv across the host link, and the other host-direct ranks copy it host-to-host after the
-// call's fence (at configs[0], P = 4 x 1 MiB, 8 MiB per call across the link -> 5 MiB).
-// Measured (profiles/r06/host_once_ab_f.jsonl, alternated A/B on one box, three runs each): the kernel
-// drops from 147.1 to 114.6 us (rocprofv3, 205 calls), but each copying rank's 1 MiB host memcpy of
-// memory the device just wrote, plus the closing rendezvous, costs more: page-locked direct calls
-// 211-242 us per call with it off against 233-255 us on, the JNI shim 298-324 against 330-348. Off.
-bool host_once_on() {
-  const char* e = getenv("MPJX_HOST_ONCE");
-  return e && *e && strcmp(e, "0") != 0;
-}
-
-// Gather every rank's whole send vector into P scratch slots (slot j = rank j); returns the slots.
+// Gather every rank's whole send vector into the one-shot slots; in[j] = rank j's vector.
 int oneshot_gather(Call& k, const void* send, int64_t count, std::vector<const void*>* in, TempStack* ts) {
   mpjx_comm* c = k.c;
   const int P = c->size, me = c->rank;
-  const size_t stride = round_up((size_t)count * k.esz, kAlignBytes);
-  CHK(k.scratch(P * stride + temp_bytes(P, count, k.esz)));
-  char* base = c->scratch;
-  *ts = TempStack{base + P * stride, c->scratch_bytes - P * stride, 0, (size_t)k.esz};
-  HIPCHK(hipMemcpyAsync(base + me * stride, send, (size_t)count * k.esz, hipMemcpyDeviceToDevice, k.s));
-  CHK(c->tr->allgather_equal(me, P, base, stride, k.s));
+  Slots S;
+  CHK(oneshot_slots(k, count, &S, ts));
+  HIPCHK(hipMemcpyAsync(S.in(me), send, (size_t)count * k.esz, hipMemcpyDeviceToDevice, k.s));
+  CHK(c->tr->allgather_equal(me, P, S.base, S.stride, k.s));
   in->resize(P);
-  for (int j = 0; j < P; j++) (*in)[j] = base + j * stride;
+  for (int j = 0; j < P; j++) (*in)[j] = S.in(j);
   return MPJX_SUCCESS;
-}
-
-size_t pipe_chunk_bytes() {
-  const char* e = getenv("MPJX_PIPE_CHUNK_MIB");
-  long m = e ? atol(e) : 0;
-  return m > 0 ? (size_t)m << 20 : 0;
 }
 
 // Chunked Allreduce (default MST order) on three streams: exchange #1 of every chunk on the call's
@@ -514,8 +590,7 @@ int allreduce_pipelined(Call& k, const char* send, char* recv, int64_t count, in
     hipEvent_t ev_in = c->pipe_ev[2 * ch], ev_out = c->pipe_ev[2 * ch + 1];
     HIPCHK(hipEventRecord(ev_in, k.s));
     HIPCHK(hipStreamWaitEvent(c->cstream, ev_in, 0));
-    for (int j = 0; j < P; j++)
-      in[j] = (j == me && !own_in_slot) ? (const void*)(send + (off + B.off[me]) * k.esz) : (const void*)S.in(j);
+    slot_inputs(S, me, own_in_slot, send + (off + B.off[me]) * k.esz, &in);
     CHK(tev(ch, 2, c->cstream));
     CHK(cb.mst(in.data(), 0, P - 1, 0, recv + (off + B.off[me]) * k.esz, B.len[me]));  // combine (chunk ch)
     CHK(tev(ch, 3, c->cstream));
@@ -553,11 +628,7 @@ static int mpjx_allreduce_impl(mpjx_comm_t c, const void* sendbuf, void* recvbuf
   if (count == 0) return k.end();
   Combine cb{op, type, flags, k.esz, k.s, nullptr};
   if (P == 1 && !force_exchange()) {  // Reduce = arraycopy(send -> recv) (:1937); Bcast = nothing
-    CHK(k.mark(0, 4));
-    CHK(k.mark(1, 4));
-    CHK(cb.copy(recv, send, count));
-    CHK(k.mark(2, 4));
-    CHK(k.mark(3, 4));
+    CHK(one_rank_copy(k, cb, recv, send, count));
     return k.end();
   }
   ncclDataType_t ndt;
@@ -580,48 +651,19 @@ static int mpjx_allreduce_impl(mpjx_comm_t c, const void* sendbuf, void* recvbuf
     CHK(direct_temps(k, P, n, &ts, (flags & MPJX_FLAG_OLD_COLLECTIVES) ? P : 0));
     cb.tmp = &ts;
     std::vector<std::vector<const void*>> all;
-    // host-direct, result across the link once (host_once_on): one device, every rank's pointers seen by
-    // rank 0, which decides for the call
-    auto* smp = lead ? dynamic_cast<SmpTransport*>(t) : nullptr;
-    if (smp) smp->w->host_out[me] = t_host_direct ? 1 : 0;
     CHK(k.mark(0, 2));
     CHK(t->share(sendbuf, (size_t)count * k.esz, recvbuf, (size_t)count * k.esz, parts, k.s, &all, lead));
     DCHK(k.mark(1, 2));
-    std::vector<const void*> in(P);
-    std::vector<void*> outs(P);
-    for (int j = 0; j < P; j++) {
-      in[j] = at(all[j][0], off, k.esz);
-      outs[j] = (void*)at(all[j][1], off, k.esz);
-    }
-    if (smp && me == 0) {
-      // Only when rank 0's own call drains its stream before the fence's rendezvous (blocking: the
-      // result is in host memory when the others pass it) and every rank gets the same MST(0) result.
-      SmpWorld& w = *smp->w;
-      int primary = -1;
-      w.copy_round = 0;
-      if ((flags & MPJX_FLAG_BLOCKING) && !(flags & MPJX_FLAG_OLD_COLLECTIVES) && host_once_on()) {
-        std::vector<void*> kept;
-        for (int j = 0; j < P; j++) {
-          w.copy_src[j] = nullptr;
-          if (w.host_out[j] && primary < 0) primary = j;
-          if (w.host_out[j] && primary != j) {
-            w.copy_src[j] = all[primary][1];
-            w.copy_round = 1;
-          } else {
-            kept.push_back(outs[j]);
-          }
-        }
-        if (w.copy_round) outs = kept;
-        w.copy_bytes = (size_t)count * k.esz;
-      }
-    }
+    std::vector<const void*> in;
+    std::vector<void*> outs;
+    direct_tables(all, off, k.esz, &in, &outs);
     bool signalled = false;  // the IPC device-sync fence flag stored from the combine kernel's tail
     if (n == 0) {
     } else if (!(flags & MPJX_FLAG_OLD_COLLECTIVES)) {
       unsigned long long tseq = 0;
       if (P <= MAXP) cb.arm_tail(t->tail_arm((size_t)count * k.esz, &tseq), tseq);  // one launch: mst_rep
-      // MST(0) range -> every rank's recv (host_once: every rank's but the copying ones')
-      const int rc = cb.mst_rep(in.data(), P, 0, outs.data(), (int)outs.size(), n);
+      // MST(0) range -> every rank's recv
+      const int rc = cb.mst_rep(in.data(), P, 0, outs.data(), P, n);
       signalled = cb.disarm_tail();
       DCHK(rc);
     } else {
@@ -634,24 +676,12 @@ static int mpjx_allreduce_impl(mpjx_comm_t c, const void* sendbuf, void* recvbuf
         for (int r = 0; r < P; r++)
           if (!(res[r] = ts.push(n))) return reject(c, fail(MPJX_ERR_INTERNAL, "scratch temporaries exhausted (P=%d)", P));
       }
-      std::vector<const void*> lst(P);
-      for (int r = 0; r < P; r++) {
-        int m = 0;
-        lst[m++] = in[r];
-        for (int i = 0; i < P; i++)
-          if (i != r) lst[m++] = in[i];
-        DCHK(cb.fold(P, lst.data(), res[r], n));
-      }
+      for (int r = 0; r < P; r++) DCHK(cb.ft(in.data(), P, r, res[r], n));
       if (alias)
         for (int r = 0; r < P; r++) DCHK(cb.copy_raw(outs[r], res[r], n));
     }
     DCHK(k.mark(2, 2));
     CHK(t->fence(k.s, lead, signalled, (flags & MPJX_FLAG_BLOCKING) != 0));
-    if (smp && smp->w->copy_round) {  // every rank reads the same copy_round after the fence's rendezvous
-      SmpWorld& w = *smp->w;
-      if (const void* src = w.copy_src[me]) memcpy(recvbuf, src, w.copy_bytes);
-      CHK(w.barrier());  // the source rank's recv stays as it is until every copy of it is done
-    }
     CHK(k.mark(3, 2));
     return k.end();
   }
@@ -665,11 +695,7 @@ static int mpjx_allreduce_impl(mpjx_comm_t c, const void* sendbuf, void* recvbuf
     if (!(flags & MPJX_FLAG_OLD_COLLECTIVES)) {
       CHK(cb.mst(in.data(), 0, P - 1, 0, recv, count));
     } else {  // FT_Allreduce: this rank's own order
-      std::vector<const void*> lst;
-      lst.push_back(in[me]);
-      for (int i = 0; i < P; i++)
-        if (i != me) lst.push_back(in[i]);
-      CHK(cb.fold(P, lst.data(), recv, count));
+      CHK(cb.ft(in.data(), P, me, recv, count));
     }
     CHK(k.mark(2, 5));
     CHK(k.mark(3, 5));
@@ -677,54 +703,30 @@ static int mpjx_allreduce_impl(mpjx_comm_t c, const void* sendbuf, void* recvbuf
   }
   if (!(flags & MPJX_FLAG_OLD_COLLECTIVES)) {
     const size_t pcb = pipe_chunk_bytes();
-    const size_t unit = (size_t)P * kAlignBytes;  // chunks split into equal aligned blocks
-    const int64_t ce = pcb ? (int64_t)(std::max(unit, pcb / unit * unit) / k.esz) : 0;
+    const int64_t ce = pcb ? (int64_t)(chunk_bytes(P, pcb) / k.esz) : 0;
     if (ce > 0 && count > ce) return allreduce_pipelined(k, send, recv, count, ce, op, type, flags);
   }
   Blocks B;
   B.even(count, P, k.esz);
   const int64_t n = B.len[me];
-  Slots S = make_slots((size_t)B.len[0] * k.esz, P);
-  CHK(k.scratch(S.bytes() + temp_bytes(P, n, k.esz)));
-  S.base = c->scratch;
-  TempStack ts{S.tail(), c->scratch_bytes - S.bytes(), 0, (size_t)k.esz};
-  cb.tmp = &ts;
-
-  bool own_in_slot = false;
+  Exchange x;
+  CHK(x.plan(k, cb, B, B.len[0]));
   CHK(k.mark(0, 1));
-  CHK(scatter_blocks(k, send, B, S, &own_in_slot));
+  CHK(x.scatter(k, send, B));
   CHK(k.mark(1, 1));
-  std::vector<const void*> in(P);
-  for (int j = 0; j < P; j++)
-    in[j] = (j == me && !own_in_slot) ? (const void*)(send + B.off[me] * k.esz) : (const void*)S.in(j);
   char* mine = recv + B.off[me] * k.esz;
   if (!(flags & MPJX_FLAG_OLD_COLLECTIVES)) {
     // MST_Reduce to root 0 then MST_Bcast: one result, the root-0 tree order, on every rank
-    CHK(cb.mst(in.data(), 0, P - 1, 0, mine, n));
+    CHK(cb.mst(x.in.data(), 0, P - 1, 0, mine, n));
     CHK(k.mark(2, 1));
+    CHK(gather_all(k, recv, B));
   } else {
     // FT_Allreduce: rank r starts from x_r and folds the others in ascending order — a different
     // order per rank, so rank me computes block me of EVERY rank's result and returns them.
-    std::vector<const void*> lst(P);
-    for (int r = 0; r < P; r++) {
-      int m = 0;
-      lst[m++] = in[r];
-      for (int i = 0; i < P; i++)
-        if (i != r) lst[m++] = in[i];
-      CHK(cb.fold(P, lst.data(), r == me ? (void*)mine : (void*)S.out(r), n));
-    }
+    for (int r = 0; r < P; r++) CHK(cb.ft(x.in.data(), P, r, r == me ? (void*)mine : (void*)x.S.out(r), n));
     CHK(k.mark(2, 1));
-    std::vector<Xfer> sends, recvs;
-    for (int j = 0; j < P; j++) {
-      if (j == me) continue;
-      if (n > 0) sends.push_back({j, S.out(j), (size_t)n * k.esz});
-      if (B.len[j] > 0) recvs.push_back({j, recv + B.off[j] * k.esz, (size_t)B.len[j] * k.esz});
-    }
-    CHK(c->tr->exchange(sends, recvs, k.s));
-    CHK(k.mark(3, 1));
-    return k.end();
+    CHK(return_blocks(k, x.S, B, recv));
   }
-  CHK(gather_all(k, recv, B));
   CHK(k.mark(3, 1));
   return k.end();
 }
@@ -732,7 +734,7 @@ static int mpjx_allreduce_impl(mpjx_comm_t c, const void* sendbuf, void* recvbuf
 static int mpjx_reduce_impl(mpjx_comm_t c, const void* sendbuf, void* recvbuf, int64_t count, int type,
                            int op, int root, unsigned flags, void* stream) {
   if (!c) return fail(MPJX_ERR_ARG, "comm is NULL");
-  if (root < 0 || root >= c->size) return fail(MPJX_ERR_ARG, "root %d out of range", root);
+  CHK(check_root(c, root));
   // recvbuf is significant at the root only — and on every rank under MPJX_FLAG_FAITHFUL, where it is
   // left as the reference leaves it (MST: the rank's sub-tree partial; FT: its own send copy)
   const bool faithful = (flags & MPJX_FLAG_FAITHFUL) != 0, old = (flags & MPJX_FLAG_OLD_COLLECTIVES) != 0;
@@ -772,91 +774,64 @@ static int mpjx_reduce_impl(mpjx_comm_t c, const void* sendbuf, void* recvbuf, i
     TempStack dts;
     DCHK(direct_temps(k, P, dn, &dts, alias ? P : 0));
     cb.tmp = &dts;
-    std::vector<const void*> in(P);
-    for (int j = 0; j < P; j++) in[j] = at(all[j][0], doff, k.esz);
-    void* out = (void*)at(all[root][1], doff, k.esz);  // straight into the root's recv
+    std::vector<const void*> in;
+    std::vector<void*> outs;  // outs[root]: straight into the root's recv
+    direct_tables(all, doff, k.esz, &in, &outs);
     if (dn == 0) {
     } else if (partials) {
-      std::vector<void*> outs(P);
-      for (int j = 0; j < P; j++) outs[j] = all[j][1] ? (void*)at(all[j][1], doff, k.esz) : nullptr;
       DCHK(mst_partials(cb, in, outs, root, dn, alias));
     } else if (!old) {
-      DCHK(cb.mst(in.data(), 0, P - 1, root, out, dn));
+      DCHK(cb.mst(in.data(), 0, P - 1, root, outs[root], dn));
     } else {
-      std::vector<const void*> lst;
-      lst.push_back(in[root]);
-      for (int i = 0; i < P; i++)
-        if (i != root) lst.push_back(in[i]);
-      DCHK(cb.fold(P, lst.data(), out, dn));
+      DCHK(cb.ft(in.data(), P, root, outs[root], dn));
     }
     CHK(t->fence(k.s, lead, false, (flags & MPJX_FLAG_BLOCKING) != 0));
     return finish();
   }
   if (!partials && oneshot((size_t)count * k.esz)) {  // small: every whole vector to the root, which reduces them all
-    const size_t stride = round_up((size_t)count * k.esz, kAlignBytes);
     const size_t bytes = (size_t)count * k.esz;
     std::vector<Xfer> sends, recvs;
-    std::vector<const void*> in(P);
     if (me != root) {
       sends.push_back({root, (void*)sendbuf, bytes});
       CHK(c->tr->exchange(sends, recvs, k.s));
       return finish();
     }
-    CHK(k.scratch(P * stride + temp_bytes(P, count, k.esz)));
-    TempStack ots{c->scratch + P * stride, c->scratch_bytes - P * stride, 0, (size_t)k.esz};
+    Slots S;
+    TempStack ots;
+    CHK(oneshot_slots(k, count, &S, &ots));
     cb.tmp = &ots;
+    std::vector<const void*> in(P);
     for (int j = 0; j < P; j++) {
-      in[j] = (j == me) ? sendbuf : (const void*)(c->scratch + j * stride);
-      if (j != me) recvs.push_back({j, c->scratch + j * stride, bytes});
+      in[j] = (j == me) ? sendbuf : (const void*)S.in(j);
+      if (j != me) recvs.push_back({j, S.in(j), bytes});
     }
     CHK(c->tr->exchange(sends, recvs, k.s));
     if (!old) {
       CHK(cb.mst(in.data(), 0, P - 1, root, recv, count));
     } else {
-      std::vector<const void*> lst;
-      lst.push_back(in[root]);
-      for (int i = 0; i < P; i++)
-        if (i != root) lst.push_back(in[i]);
-      CHK(cb.fold(P, lst.data(), recv, count));
+      CHK(cb.ft(in.data(), P, root, recv, count));
     }
     return k.end();
   }
-  Slots S = make_slots((size_t)B.len[0] * k.esz, P);
-  CHK(k.scratch(S.bytes() + temp_bytes(P, n, k.esz)));
-  S.base = c->scratch;
-  TempStack ts{S.tail(), c->scratch_bytes - S.bytes(), 0, (size_t)k.esz};
-  cb.tmp = &ts;
-
-  bool own_in_slot = false;
-  CHK(scatter_blocks(k, send, B, S, &own_in_slot));
-  std::vector<const void*> in(P);
-  for (int j = 0; j < P; j++)
-    in[j] = (j == me && !own_in_slot) ? (const void*)(send + B.off[me] * k.esz) : (const void*)S.in(j);
-  std::vector<Xfer> sends, recvs;
+  Exchange x;
+  CHK(x.plan(k, cb, B, B.len[0]));
+  CHK(x.scatter(k, send, B));
   if (partials) {
     // block me of every rank's partial, then each block to its rank (the exchange Scan uses)
     std::vector<void*> outs(P);
-    for (int j = 0; j < P; j++) outs[j] = (j == me) ? (void*)(recv + B.off[me] * k.esz) : (void*)S.out(j);
-    CHK(mst_partials(cb, in, outs, root, n, false, me));  // outs[me] may alias in[me] (in place)
-    for (int j = 0; j < P; j++) {
-      if (j == me) continue;
-      if (n > 0) sends.push_back({j, S.out(j), (size_t)n * k.esz});
-      if (B.len[j] > 0) recvs.push_back({j, recv + B.off[j] * k.esz, (size_t)B.len[j] * k.esz});
-    }
-    CHK(c->tr->exchange(sends, recvs, k.s));
+    for (int j = 0; j < P; j++) outs[j] = (j == me) ? (void*)(recv + B.off[me] * k.esz) : (void*)x.S.out(j);
+    CHK(mst_partials(cb, x.in, outs, root, n, false, me));  // outs[me] may alias in[me] (in place)
+    CHK(return_blocks(k, x.S, B, recv));
     return k.end();
   }
-  void* out = (me == root) ? (void*)(recv + B.off[me] * k.esz) : (void*)S.out(0);
+  void* out = (me == root) ? (void*)(recv + B.off[me] * k.esz) : (void*)x.S.out(0);
   if (!old) {
-    CHK(cb.mst(in.data(), 0, P - 1, root, out, n));  // MST_Reduce rooted at `root`
+    CHK(cb.mst(x.in.data(), 0, P - 1, root, out, n));  // MST_Reduce rooted at `root`
   } else {
-    std::vector<const void*> lst;  // FT_Reduce: x_root, then ranks 0..P-1 (skipping root) folded in
-    lst.push_back(in[root]);
-    for (int i = 0; i < P; i++)
-      if (i != root) lst.push_back(in[i]);
-    CHK(cb.fold(P, lst.data(), out, n));
+    CHK(cb.ft(x.in.data(), P, root, out, n));  // FT_Reduce: x_root, then ranks 0..P-1 (skipping root) folded in
   }
   // gather the reduced blocks at the root
+  std::vector<Xfer> sends, recvs;
   if (me != root) {
     if (n > 0) sends.push_back({root, out, (size_t)n * k.esz});
   } else {
@@ -892,11 +867,7 @@ static int mpjx_reduce_scatter_impl(mpjx_comm_t c, const void* sendbuf, void* re
   const int64_t n = B.len[me];
   Combine cb{op, type, flags, k.esz, k.s, nullptr};
   if (P == 1) {
-    CHK(k.mark(0, 4));
-    CHK(k.mark(1, 4));
-    CHK(cb.copy(recv, send, n));
-    CHK(k.mark(2, 4));
-    CHK(k.mark(3, 4));
+    CHK(one_rank_copy(k, cb, recv, send, n));
     return k.end();
   }
   // MPJX_FLAG_FAITHFUL: the BKT ring (default collectives, typed ops) leaves its arr in sendbuf
@@ -947,19 +918,12 @@ static int mpjx_reduce_scatter_impl(mpjx_comm_t c, const void* sendbuf, void* re
     if (bkt_send) CHK(bkt_sendbuf(k, cb, (char*)sendbuf, total, B.off[me], n, recv, P));
     return k.end();
   }
-  Slots S = make_slots((size_t)n * k.esz, P);
-  CHK(k.scratch(S.bytes() + temp_bytes(P, n, k.esz) + kAlignBytes));
-  S.base = c->scratch;
-  TempStack ts{S.tail(), c->scratch_bytes - S.bytes(), 0, (size_t)k.esz};
-  cb.tmp = &ts;
-
-  bool own_in_slot = false;
+  Exchange x;
+  CHK(x.plan(k, cb, B, n, kAlignBytes));  // slots of this rank's own block: the blocks differ in size
   CHK(k.mark(0, 1));
-  CHK(scatter_blocks(k, send, B, S, &own_in_slot));
+  CHK(x.scatter(k, send, B));
   CHK(k.mark(1, 1));
-  std::vector<const void*> in(P);
-  for (int j = 0; j < P; j++)
-    in[j] = (j == me && !own_in_slot) ? (const void*)(send + B.off[me] * k.esz) : (const void*)S.in(j);
+  const std::vector<const void*>& in = x.in;
   if (flags & MPJX_FLAG_OLD_COLLECTIVES) {
     // FT_Reduce_scatter = FT_Reduce(root 0) + Scatter: x_0 folded with x_1 .. x_{P-1}
     CHK(cb.fold(P, in.data(), recv, n));
@@ -992,11 +956,7 @@ static int mpjx_scan_impl(mpjx_comm_t c, const void* sendbuf, void* recvbuf, int
   if (count == 0) return k.end();
   Combine cb{op, type, flags, k.esz, k.s, nullptr};
   if (P == 1) {
-    CHK(k.mark(0, 4));
-    CHK(k.mark(1, 4));
-    CHK(cb.copy(recv, send, count));
-    CHK(k.mark(2, 4));
-    CHK(k.mark(3, 4));
+    CHK(one_rank_copy(k, cb, recv, send, count));
     return k.end();
   }
   Blocks B;
@@ -1014,12 +974,9 @@ static int mpjx_scan_impl(mpjx_comm_t c, const void* sendbuf, void* recvbuf, int
     CHK(k.mark(0, 2));
     CHK(t->share(sendbuf, (size_t)count * k.esz, recvbuf, (size_t)count * k.esz, parts, k.s, &all, lead));
     DCHK(k.mark(1, 2));
-    std::vector<const void*> in(P);
-    std::vector<void*> outs(P);
-    for (int j = 0; j < P; j++) {
-      in[j] = at(all[j][0], doff, k.esz);
-      outs[j] = (void*)at(all[j][1], doff, k.esz);  // this range of rank j's prefix -> rank j
-    }
+    std::vector<const void*> in;
+    std::vector<void*> outs;  // this range of rank j's prefix -> rank j
+    direct_tables(all, doff, k.esz, &in, &outs);
     unsigned long long tseq = 0;  // one K_SCAN launch at P <= 8
     if (P <= MAXP) cb.arm_tail(t->tail_arm((size_t)count * k.esz, &tseq), tseq);
     const int src = cb.scan(P, in.data(), outs.data(), dn);
@@ -1037,41 +994,22 @@ static int mpjx_scan_impl(mpjx_comm_t c, const void* sendbuf, void* recvbuf, int
     CHK(oneshot_gather(k, sendbuf, count, &all, &ots));
     CHK(k.mark(1, 5));
     cb.tmp = &ots;
-    std::vector<const void*> lst;
-    lst.push_back(all[me]);
-    for (int i = 0; i < me; i++) lst.push_back(all[i]);
-    CHK(cb.fold(me + 1, lst.data(), recv, count));
+    CHK(cb.prefix(all.data(), me, recv, count));
     CHK(k.mark(2, 5));
     CHK(k.mark(3, 5));
     return k.end();
   }
-  Slots S = make_slots((size_t)B.len[0] * k.esz, P);
-  CHK(k.scratch(S.bytes() + temp_bytes(P, n, k.esz)));
-  S.base = c->scratch;
-  TempStack ts{S.tail(), c->scratch_bytes - S.bytes(), 0, (size_t)k.esz};
-  cb.tmp = &ts;
-
-  bool own_in_slot = false;
+  Exchange x;
+  CHK(x.plan(k, cb, B, B.len[0]));
   CHK(k.mark(0, 1));
-  CHK(scatter_blocks(k, send, B, S, &own_in_slot));
+  CHK(x.scatter(k, send, B));
   CHK(k.mark(1, 1));
-  std::vector<const void*> in(P);
   std::vector<void*> out(P);
-  char* mine = recv + B.off[me] * k.esz;
-  for (int j = 0; j < P; j++) {
-    in[j] = (j == me && !own_in_slot) ? (const void*)(send + B.off[me] * k.esz) : (const void*)S.in(j);
-    out[j] = (j == me) ? (void*)mine : (void*)S.out(j);
-  }
+  for (int j = 0; j < P; j++) out[j] = (j == me) ? (void*)(recv + B.off[me] * k.esz) : (void*)x.S.out(j);
   // block me of every rank's prefix, each in the reference's fold order
-  CHK(cb.scan(P, in.data(), out.data(), n));
+  CHK(cb.scan(P, x.in.data(), out.data(), n));
   CHK(k.mark(2, 1));
-  std::vector<Xfer> sends, recvs;
-  for (int j = 0; j < P; j++) {
-    if (j == me) continue;
-    if (n > 0) sends.push_back({j, S.out(j), (size_t)n * k.esz});
-    if (B.len[j] > 0) recvs.push_back({j, recv + B.off[j] * k.esz, (size_t)B.len[j] * k.esz});
-  }
-  CHK(c->tr->exchange(sends, recvs, k.s));
+  CHK(return_blocks(k, x.S, B, recv));
   CHK(k.mark(3, 1));
   return k.end();
 }
@@ -1079,7 +1017,7 @@ static int mpjx_scan_impl(mpjx_comm_t c, const void* sendbuf, void* recvbuf, int
 static int bcast_entry(mpjx_comm_t c, void* buf, int64_t count, int type, int root, void* stream) {
   if (!c) return fail(MPJX_ERR_ARG, "comm is NULL");
   if (mpjx_type_size(type) == 0) return fail(MPJX_ERR_ARG, "unknown datatype code %d", type);
-  if (root < 0 || root >= c->size) return fail(MPJX_ERR_ARG, "root %d out of range", root);
+  CHK(check_root(c, root));
   if (count < 0 || (count > 0 && !buf)) return reject(c, fail(MPJX_ERR_ARG, "bad buffer/count"));
   if (count > 0) CHK(check_bufs(c, buf, nullptr));
   Call k;
@@ -1119,7 +1057,7 @@ static int gather_entry(mpjx_comm_t c, const void* sendbuf, void* recvbuf, int64
                         void* stream) {
   if (!c) return fail(MPJX_ERR_ARG, "comm is NULL");
   if (mpjx_type_size(type) == 0) return fail(MPJX_ERR_ARG, "unknown datatype code %d", type);
-  if (root < 0 || root >= c->size) return fail(MPJX_ERR_ARG, "root %d out of range", root);
+  CHK(check_root(c, root));
   if (count < 0 || (count > 0 && (!sendbuf || (c->rank == root && !recvbuf))))
     return reject(c, fail(MPJX_ERR_ARG, "bad buffer/count"));
   if (count > 0) CHK(check_bufs(c, sendbuf, c->rank == root ? recvbuf : nullptr));
@@ -1144,7 +1082,7 @@ static int scatter_entry(mpjx_comm_t c, const void* sendbuf, void* recvbuf, int6
                          void* stream) {
   if (!c) return fail(MPJX_ERR_ARG, "comm is NULL");
   if (mpjx_type_size(type) == 0) return fail(MPJX_ERR_ARG, "unknown datatype code %d", type);
-  if (root < 0 || root >= c->size) return fail(MPJX_ERR_ARG, "root %d out of range", root);
+  CHK(check_root(c, root));
   if (count < 0 || (count > 0 && (!recvbuf || (c->rank == root && !sendbuf))))
     return reject(c, fail(MPJX_ERR_ARG, "bad buffer/count"));
   if (count > 0) CHK(check_bufs(c, recvbuf, c->rank == root ? sendbuf : nullptr));
@@ -1194,31 +1132,38 @@ int finish_blocking(mpjx_comm* c, unsigned flags, void* stream) {
   if (!(flags & MPJX_FLAG_BLOCKING)) return MPJX_SUCCESS;
   return c->tr->wait(stream ? (hipStream_t)stream : c->stream);
 }
+
+// An element-wise collective over its windows: impl(send, recv, count, flags) once per window (once for
+// an empty call), then the blocking call's drain
+template <class Fn>
+int windowed(mpjx_comm* c, const void* sendbuf, void* recvbuf, int64_t count, int type, unsigned flags, void* stream,
+             Fn impl) {
+  HIPCHK(hipSetDevice(c->device));
+  const int64_t we = window_elems(c, type);
+  for (int64_t off = 0; off < count || off == 0; off += we)
+    CHK(impl(cadv(sendbuf, off, type), (void*)cadv(recvbuf, off, type), std::min(we, count - off),
+             window_flags(flags, off + we >= count)));
+  return finish_blocking(c, flags, stream);
+}
 }  // namespace
 
 static int allreduce_entry(mpjx_comm_t c, const void* sendbuf, void* recvbuf, int64_t count, int type, int op,
                            unsigned flags, void* stream) {
   CHK(validate(c, sendbuf, recvbuf, count, type, op, true));
-  HIPCHK(hipSetDevice(c->device));
-  const int64_t we = window_elems(c, type);
-  for (int64_t off = 0; off < count || off == 0; off += we)
-    CHK(mpjx_allreduce_impl(c, cadv(sendbuf, off, type), (void*)cadv(recvbuf, off, type), std::min(we, count - off),
-                            type, op, window_flags(flags, off + we >= count), stream));
-  return finish_blocking(c, flags, stream);
+  return windowed(c, sendbuf, recvbuf, count, type, flags, stream, [&](const void* s, void* r, int64_t n, unsigned f) {
+    return mpjx_allreduce_impl(c, s, r, n, type, op, f, stream);
+  });
 }
 
 static int reduce_entry(mpjx_comm_t c, const void* sendbuf, void* recvbuf, int64_t count, int type, int op,
                         int root, unsigned flags, void* stream) {
   if (!c) return fail(MPJX_ERR_ARG, "comm is NULL");
-  if (root < 0 || root >= c->size) return fail(MPJX_ERR_ARG, "root %d out of range", root);
+  CHK(check_root(c, root));
   const bool all_recv = c->rank == root || (flags & MPJX_FLAG_FAITHFUL);
   CHK(validate(c, sendbuf, all_recv ? recvbuf : sendbuf, count, type, op, true));
-  HIPCHK(hipSetDevice(c->device));
-  const int64_t we = window_elems(c, type);
-  for (int64_t off = 0; off < count || off == 0; off += we)
-    CHK(mpjx_reduce_impl(c, cadv(sendbuf, off, type), (void*)cadv(recvbuf, off, type), std::min(we, count - off),
-                         type, op, root, window_flags(flags, off + we >= count), stream));
-  return finish_blocking(c, flags, stream);
+  return windowed(c, sendbuf, recvbuf, count, type, flags, stream, [&](const void* s, void* r, int64_t n, unsigned f) {
+    return mpjx_reduce_impl(c, s, r, n, type, op, root, f, stream);
+  });
 }
 
 static int reduce_scatter_entry(mpjx_comm_t c, const void* sendbuf, void* recvbuf, const int64_t* recvcounts,
@@ -1255,12 +1200,9 @@ static int reduce_scatter_entry(mpjx_comm_t c, const void* sendbuf, void* recvbu
 static int scan_entry(mpjx_comm_t c, const void* sendbuf, void* recvbuf, int64_t count, int type, int op,
                       unsigned flags, void* stream) {
   CHK(validate(c, sendbuf, recvbuf, count, type, op, true));
-  HIPCHK(hipSetDevice(c->device));
-  const int64_t we = window_elems(c, type);
-  for (int64_t off = 0; off < count || off == 0; off += we)
-    CHK(mpjx_scan_impl(c, cadv(sendbuf, off, type), (void*)cadv(recvbuf, off, type), std::min(we, count - off), type,
-                       op, window_flags(flags, off + we >= count), stream));
-  return finish_blocking(c, flags, stream);
+  return windowed(c, sendbuf, recvbuf, count, type, flags, stream, [&](const void* s, void* r, int64_t n, unsigned f) {
+    return mpjx_scan_impl(c, s, r, n, type, op, f, stream);
+  });
 }
 
 extern "C" int mpjx_comm_phase_timing(mpjx_comm_t c, int enable) {
@@ -1332,12 +1274,6 @@ extern "C" int mpjx_mpjbuf_section(const void* buf, int64_t nbytes, int64_t pos,
 // and the collective overlap (full duplex). Every rank walks the chunks in the same order.
 
 namespace {
-size_t host_chunk_bytes() {  // MPJX_HOST_CHUNK_MIB (read per call) overrides the pipeline granularity
-  const char* e = getenv("MPJX_HOST_CHUNK_MIB");
-  const long m = e ? atol(e) : 0;
-  return (size_t)(m > 0 ? m : 16) << 20;
-}
-
 int host_stage(Call& k, size_t bytes) { return grow_device(k.c, &k.c->hstage, &k.c->hstage_bytes, bytes, k.s); }
 
 // The allocation holding p (page-locked host memory, hipHostMalloc'd or hipHostRegister'ed, or device
@@ -1387,14 +1323,18 @@ hipError_t host_copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kin
   return hipSuccess;
 }
 
-bool host_pinned(const void* p, size_t bytes) {
+// [p, p + bytes) is page-locked host memory inside ONE allocation; `identity`: and the device addresses
+// it at the same pointer
+bool host_locked(const void* p, size_t bytes, bool identity) {
   hipPointerAttribute_t a{};
   if (hipPointerGetAttributes(&a, p) != hipSuccess) {
     (void)hipGetLastError();  // pageable memory: the query fails, and must not leave a sticky error
     return false;
   }
-  return a.type == hipMemoryTypeHost && in_one_allocation(p, bytes);
+  return a.type == hipMemoryTypeHost && (!identity || a.devicePointer == p) && in_one_allocation(p, bytes);
 }
+
+bool host_pinned(const void* p, size_t bytes) { return host_locked(p, bytes, false); }
 
 // [p, p + bytes) is page-locked host memory the device addresses at the same pointer (hipHostMalloc'd,
 // e.g. through mpjx_host_alloc), inside ONE allocation: a kernel can load and store it as it is.
@@ -1402,14 +1342,7 @@ bool host_pinned(const void* p, size_t bytes) {
 // against the allocation's own start and size: a range that starts in one page-locked
 // block and ends in another, with pageable or unmapped memory between, passed a first-and-last-byte
 // check and would have reached a kernel as a GPU fault; it now takes the staged form.
-bool host_identity_mapped(const void* p, size_t bytes) {
-  hipPointerAttribute_t a{};
-  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-    (void)hipGetLastError();  // pageable memory: the query fails, and must not leave a sticky error
-    return false;
-  }
-  return a.type == hipMemoryTypeHost && a.devicePointer == p && in_one_allocation(p, bytes);
-}
+bool host_identity_mapped(const void* p, size_t bytes) { return host_locked(p, bytes, true); }
 
 // The host-direct form of the *_host calls (round 5). Multicore mode with every rank on ONE device (the
 // direct engine's single-launch form), a call that is one host-pipeline chunk on every rank (count <=
@@ -1422,13 +1355,11 @@ bool host_identity_mapped(const void* p, size_t bytes) {
 // meet in the same direct call. The JNI shim's multicore staging is page-locked for this reason.
 // MPJX_HOST_DIRECT=0 turns it off.
 bool host_direct_ok(mpjx_comm* c, int64_t count, int type, std::initializer_list<std::pair<const void*, size_t>> bufs) {
-  const char* e = getenv("MPJX_HOST_DIRECT");
-  if (e && *e && strcmp(e, "0") == 0) return false;
+  if (host_direct_off()) return false;
   Direct* t = smp_direct(c);
   if (!t || !t->single()) return false;
-  const size_t esz = (size_t)mpjx_type_size(type), unit = (size_t)c->size * kAlignBytes;
-  const size_t cb = std::max(unit, host_chunk_bytes() / unit * unit);
-  if (!esz || count > (int64_t)(cb / esz)) return false;
+  const size_t esz = (size_t)mpjx_type_size(type);
+  if (!esz || count > (int64_t)(chunk_bytes(c->size, host_chunk_bytes()) / esz)) return false;
   for (const auto& b : bufs)
     if (b.first && b.second && !host_identity_mapped(b.first, b.second)) return false;
   return true;
@@ -1457,9 +1388,7 @@ int host_pipeline(mpjx_comm* c, const void* sendbuf, void* recvbuf, int64_t coun
   const size_t esz = (size_t)k.esz, bytes = (size_t)count * esz, half = round_up(bytes, kAlignBytes);
   CHK(host_stage(k, 2 * half + kAlignBytes));
   char *ds = c->hstage, *dr = c->hstage + half;
-  // chunk = multiple of P x 256 B so every chunk splits into equal, aligned blocks
-  const size_t unit = (size_t)c->size * kAlignBytes;
-  const size_t cb = std::max(unit, host_chunk_bytes() / unit * unit);
+  const size_t cb = chunk_bytes(c->size, host_chunk_bytes());
   const int64_t ce = (int64_t)(cb / esz);
   const int64_t nchunks = (count + ce - 1) / ce;
   if (nchunks <= 1) {  // small: one chunk, on the call's stream
@@ -1563,6 +1492,25 @@ int host_pipeline(mpjx_comm* c, const void* sendbuf, void* recvbuf, int64_t coun
   if (se != hipSuccess) return fail(MPJX_ERR_HIP, "host pipeline: %s", hipGetErrorString(se));
   return k.end();
 }
+
+// An element-wise *_host call, arguments validated: the host-direct form — call(send, recv, count, flags,
+// stream) on the host buffers, blocking — if this rank's buffers qualify, else the chunk pipeline over
+// `call`. out_here: recvbuf is significant on this rank.
+template <class Fn>
+int host_call(mpjx_comm* c, const void* sendbuf, void* recvbuf, int64_t count, int type, unsigned flags, bool out_here,
+              Fn call) {
+  if (count == 0) return MPJX_SUCCESS;
+  const size_t bytes = (size_t)count * mpjx_type_size(type);
+  void* out = out_here ? recvbuf : nullptr;
+  if (host_direct_ok(c, count, type, {{sendbuf, bytes}, {out, bytes}})) {
+    c->host_form = 2;
+    return call(sendbuf, out, count, flags | MPJX_FLAG_BLOCKING, nullptr);
+  }
+  c->host_form = 1;
+  return host_pipeline(c, sendbuf, recvbuf, count, type, out_here, [&](char* ds, char* dr, int64_t n, hipStream_t s) {
+    return call(ds, dr, n, flags, s);
+  });
+}
 }  // namespace
 
 extern "C" int mpjx_host_alloc(void** ptr, int64_t bytes) {
@@ -1581,56 +1529,33 @@ static int allreduce_host_entry(mpjx_comm_t c, const void* sendbuf, void* recvbu
                                 int op, unsigned flags) {
   flags &= ~MPJX_FLAG_BLOCKING;  // synchronous anyway; the chunks' collectives must stay asynchronous
   CHK(validate(c, sendbuf, recvbuf, count, type, op));
-  if (count == 0) return MPJX_SUCCESS;
-  const size_t bytes = (size_t)count * mpjx_type_size(type);
-  if (host_direct_ok(c, count, type, {{sendbuf, bytes}, {recvbuf, bytes}})) {
-    c->host_form = 2;
-    HostDirectScope hd;
-    return mpjx_allreduce(c, sendbuf, recvbuf, count, type, op, flags | MPJX_FLAG_BLOCKING, nullptr);
-  }
-  c->host_form = 1;
-  return host_pipeline(c, sendbuf, recvbuf, count, type, true, [&](char* ds, char* dr, int64_t n, hipStream_t s) {
-    return mpjx_allreduce(c, ds, dr, n, type, op, flags, s);
-  });
+  return host_call(c, sendbuf, recvbuf, count, type, flags, true,
+                   [&](const void* s, void* r, int64_t n, unsigned f, void* stream) {
+                     return mpjx_allreduce(c, s, r, n, type, op, f, stream);
+                   });
 }
 
 static int reduce_host_entry(mpjx_comm_t c, const void* sendbuf, void* recvbuf, int64_t count, int type,
                              int op, int root, unsigned flags) {
   flags &= ~MPJX_FLAG_BLOCKING;  // synchronous anyway; the chunks' collectives must stay asynchronous
   if (!c) return fail(MPJX_ERR_ARG, "comm is NULL");
-  if (root < 0 || root >= c->size) return fail(MPJX_ERR_ARG, "root %d out of range", root);
+  CHK(check_root(c, root));
   const bool all_recv = c->rank == root || (flags & MPJX_FLAG_FAITHFUL);  // faithful: every rank's recvbuf
   CHK(validate(c, sendbuf, all_recv ? recvbuf : sendbuf, count, type, op));
-  if (count == 0) return MPJX_SUCCESS;
-  const size_t bytes = (size_t)count * mpjx_type_size(type);
-  if (host_direct_ok(c, count, type, {{sendbuf, bytes}, {all_recv ? recvbuf : nullptr, bytes}})) {
-    c->host_form = 2;
-    HostDirectScope hd;
-    return mpjx_reduce(c, sendbuf, all_recv ? recvbuf : nullptr, count, type, op, root, flags | MPJX_FLAG_BLOCKING,
-                       nullptr);
-  }
-  c->host_form = 1;
-  return host_pipeline(c, sendbuf, recvbuf, count, type, all_recv,
-                       [&](char* ds, char* dr, int64_t n, hipStream_t s) {
-                         return mpjx_reduce(c, ds, dr, n, type, op, root, flags, s);
-                       });
+  return host_call(c, sendbuf, recvbuf, count, type, flags, all_recv,
+                   [&](const void* s, void* r, int64_t n, unsigned f, void* stream) {
+                     return mpjx_reduce(c, s, r, n, type, op, root, f, stream);
+                   });
 }
 
 static int scan_host_entry(mpjx_comm_t c, const void* sendbuf, void* recvbuf, int64_t count, int type,
                            int op, unsigned flags) {
   flags &= ~MPJX_FLAG_BLOCKING;  // synchronous anyway; the chunks' collectives must stay asynchronous
   CHK(validate(c, sendbuf, recvbuf, count, type, op));
-  if (count == 0) return MPJX_SUCCESS;
-  const size_t bytes = (size_t)count * mpjx_type_size(type);
-  if (host_direct_ok(c, count, type, {{sendbuf, bytes}, {recvbuf, bytes}})) {
-    c->host_form = 2;
-    HostDirectScope hd;
-    return mpjx_scan(c, sendbuf, recvbuf, count, type, op, flags | MPJX_FLAG_BLOCKING, nullptr);
-  }
-  c->host_form = 1;
-  return host_pipeline(c, sendbuf, recvbuf, count, type, true, [&](char* ds, char* dr, int64_t n, hipStream_t s) {
-    return mpjx_scan(c, ds, dr, n, type, op, flags, s);
-  });
+  return host_call(c, sendbuf, recvbuf, count, type, flags, true,
+                   [&](const void* s, void* r, int64_t n, unsigned f, void* stream) {
+                     return mpjx_scan(c, s, r, n, type, op, f, stream);
+                   });
 }
 
 static int reduce_scatter_host_entry(mpjx_comm_t c, const void* sendbuf, void* recvbuf,
@@ -1646,7 +1571,6 @@ static int reduce_scatter_host_entry(mpjx_comm_t c, const void* sendbuf, void* r
   const size_t esz = (size_t)mpjx_type_size(type);
   if (total > 0 && host_direct_ok(c, total, type, {{sendbuf, (size_t)total * esz}, {recvbuf, (size_t)std::max<int64_t>(mine, 0) * esz}})) {
     c->host_form = 2;
-    HostDirectScope hd;
     return mpjx_reduce_scatter(c, sendbuf, mine > 0 ? recvbuf : nullptr, recvcounts, type, op,
                                flags | MPJX_FLAG_BLOCKING, nullptr);
   }

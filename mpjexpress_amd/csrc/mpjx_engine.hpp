@@ -161,16 +161,6 @@ struct SmpWorld {
   std::vector<char> synced;  // fence(): the rank's stream drained before the rendezvous (no done[] wait)
   int refs = 0;
   std::atomic<int> failed{0};  // a rank left a collective early: every barrier fails from now on
-  // Host-direct Allreduce, result across the host link once (mpjx_collectives.hip, host_once): before
-  // share() each rank says whether its recv is page-locked host memory of a synchronous *_host call
-  // (host_out); rank 0, launching for all, writes the result into the first such rank's recv only and
-  // names it in copy_src[r] for the other such ranks, which copy it host-to-host after the fence.
-  // copy_round (set by rank 0 before the fence's barrier, so every rank reads the same value after it):
-  // the call ends with one more rendezvous, once every copy is done.
-  std::vector<char> host_out;
-  std::vector<const void*> copy_src;
-  size_t copy_bytes = 0;
-  int copy_round = 0;
   int barrier();
   void abort();
 };

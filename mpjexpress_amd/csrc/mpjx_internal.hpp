@@ -54,6 +54,12 @@ int comm_common_init(mpjx_comm* c);
 
 namespace mpjx {
 
+// MPJX_ERR_ARG unless `root` is a rank of c (c checked by COMM_ARG or its like before)
+inline int check_root(const mpjx_comm* c, int root) {
+  if (root < 0 || root >= c->size) return fail(MPJX_ERR_ARG, "root %d out of range", root);
+  return MPJX_SUCCESS;
+}
+
 // Stack of device temporaries for P > MAXP compositions (carved from the comm scratch tail).
 struct TempStack {
   char* base = nullptr;
@@ -172,6 +178,27 @@ struct Combine {
   }
   int fold(int P, const void* const* in, void* out, int64_t n) { return fold_o(P, in, false, out, true, n); }
 
+  // The fold list of ft() and prefix(): one allocation serves every fold of a call
+  std::vector<const void*> order;
+  // FT order: in[first] folded with every other rank ascending (FT_Allreduce's result on rank `first`,
+  // FT_Reduce's at root `first`)
+  int ft(const void* const* in, int P, int first, void* out, int64_t n) {
+    order.clear();
+    order.reserve(P);
+    order.push_back(in[first]);
+    for (int i = 0; i < P; i++)
+      if (i != first) order.push_back(in[i]);
+    return fold(P, order.data(), out, n);
+  }
+  // Scan's order for rank r: out = in[r-1] (op) (... (in[0] (op) in[r])), in[r] folded with in[0..r-1]
+  int prefix(const void* const* in, int r, void* out, int64_t n) {
+    order.clear();
+    order.reserve(r + 1);
+    order.push_back(in[r]);
+    order.insert(order.end(), in, in + r);
+    return fold(r + 1, order.data(), out, n);
+  }
+
   // out = MST_Reduce tree over in[l..r] (leaves) rooted at `root` (absolute rank index)
   int mst_o(const void* const* in, int l, int r, int root, void* out, bool out_final, int64_t n) {
     if (n <= 0) return MPJX_SUCCESS;
@@ -222,13 +249,8 @@ struct Combine {
       a.n = n;
       return launch(K_SCAN, P, a, leaf_mask(P), rbe());
     }
-    std::vector<const void*> lst;
-    for (int r = P - 1; r >= 0; r--) {  // descending: out[r] may alias in[r], which only ranks > r read
-      lst.clear();
-      lst.push_back(in[r]);
-      for (int i = 0; i < r; i++) lst.push_back(in[i]);
-      CHK(fold((int)lst.size(), lst.data(), out[r], n));
-    }
+    // descending: out[r] may alias in[r], which only ranks > r read
+    for (int r = P - 1; r >= 0; r--) CHK(prefix(in, r, out[r], n));
     return MPJX_SUCCESS;
   }
 

@@ -469,8 +469,6 @@ extern "C" int mpjx_comm_init_smp(mpjx_comm_t* comms, int nranks, const int* dev
   w->shared.resize(nranks);
   w->idle.assign(nranks, 0);
   w->synced.assign(nranks, 0);
-  w->host_out.assign(nranks, 0);
-  w->copy_src.assign(nranks, nullptr);
   w->direct = true;
   w->single = std::all_of(devices, devices + nranks, [&](int d) { return d == devices[0]; });
   w->ready.assign(nranks, nullptr);

@@ -621,8 +621,7 @@ def latency(out, P=4, calls=int(os.environ.get("MPJX_JNI_LATENCY_CALLS", "50")))
 def main():
     mode = sys.argv[1] if len(sys.argv) > 1 else "gpu"
     if mode == "latency":
-        out = {"MPJX_HOST_DIRECT": os.environ.get("MPJX_HOST_DIRECT", "1"),
-               "MPJX_HOST_ONCE": os.environ.get("MPJX_HOST_ONCE", "1")}
+        out = {"MPJX_HOST_DIRECT": os.environ.get("MPJX_HOST_DIRECT", "1")}
         latency(out)
         print(json.dumps(out), flush=True)
         return

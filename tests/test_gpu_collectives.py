@@ -619,7 +619,7 @@ def test_host_pipeline_multichunk():
     assert np.array_equal(out[1][2].view(np.uint64), exp_rd.view(np.uint64))
 
 
-@pytest.mark.parametrize("mix", ["all_direct", "mixed", "direct_off", "chunk_edge", "once_on", "mixed_rank0_staged"])
+@pytest.mark.parametrize("mix", ["all_direct", "mixed", "direct_off", "chunk_edge", "mixed_rank0_staged"])
 def test_host_direct_form_multicore(mix, monkeypatch):
     """The *_host calls' host-direct form (round 5): multicore mode, every rank on one device, a call of
     one host-pipeline chunk, page-locked buffers from mpjx_host_alloc — the P-way kernel reads and writes
@@ -628,10 +628,7 @@ def test_host_direct_form_multicore(mix, monkeypatch):
     mixed, with 1 MiB host chunks, at exactly one chunk (direct) and one element more (every rank
     pipelines: two chunks). Allreduce, Reduce (root 3, and a faithful Reduce writing every rank's
     recvbuf), Scan and a ragged Reduce_scatter, at 1001 elements and 1 MiB, all bit-exact vs the oracle.
-    The form each rank took is read back (mpjx_comm_last_host_form). `once_on`: MPJX_HOST_ONCE=1, the
-    host-direct Allreduce writes its result across the link once (into the first
-    host-direct rank's recvbuf; the others copy it host-to-host inside the call; off by default, slower
-    per call); `mixed_rank0_staged`: odd ranks direct, so the launching rank 0 is staged."""
+    The form each rank took is read back (mpjx_comm_last_host_form). `mixed_rank0_staged`: odd ranks direct, so the launching rank 0 is staged."""
     import ctypes
 
     from mpjexpress_amd import _lib, mpi
@@ -639,8 +636,6 @@ def test_host_direct_form_multicore(mix, monkeypatch):
 
     if mix == "direct_off":
         monkeypatch.setenv("MPJX_HOST_DIRECT", "0")
-    if mix == "once_on":
-        monkeypatch.setenv("MPJX_HOST_ONCE", "1")
     sizes = (1001, (1 << 20) // 8)
     if mix == "chunk_edge":
         monkeypatch.setenv("MPJX_HOST_CHUNK_MIB", "1")

@@ -18,7 +18,6 @@
 #   launch1_budget5 / launch1_hard  world-1 self-launch with --budget-s 5 (optional phases skipped) /
 #                 --hard-s 30 with the e2e_host phase stalled (MPJX_BENCH_STALL_PHASE): the line so far, cut_short
 #   jni_latency   configs[0] (1 MiB, P = 4 rank threads) through the JNI shim + stand-in JNIEnv, per call
-#   host_once_ab / host_once_prof  the same with MPJX_HOST_ONCE=1/0 alternated / their kernel stats
 #   census        tools/queue_census.py: hardware queues of the P = 8 one-GPU IPC worlds vs what the GPU maps
 #   load_cost     tools/load_cost: dlopen / runtime init / comm init / first and later calls (no torch)
 #   load_cost_ab  the same, 3 x alternating the shipped library and mpjexpress_amd/lib_cz (compressed fatbin)
@@ -110,15 +109,6 @@ for step in "$@"; do
             tail -9 "$OUT/${TAG}_census_forced.log" ;;
     census) run census 600 bash -c "python tools/queue_census.py '$OUT/${TAG}_census.json' > '$OUT/${TAG}_census.log' 2>&1"
             tail -3 "$OUT/${TAG}_census.log" ;;
-    host_once_ab)  # host-direct Allreduce result across the link once (MPJX_HOST_ONCE=1) or to every rank (0), alternated
-      for i in 1 2 3; do
-        run once_on$i 200 bash -c "MPJX_HOST_ONCE=1 python tests/jni_driver.py latency >> '$OUT/${TAG}_host_once_ab.jsonl' 2>> '$OUT/${TAG}_host_once_ab.err'"
-        run once_off$i 200 bash -c "MPJX_HOST_ONCE=0 python tests/jni_driver.py latency >> '$OUT/${TAG}_host_once_ab.jsonl' 2>> '$OUT/${TAG}_host_once_ab.err'"
-      done
-      cat "$OUT/${TAG}_host_once_ab.jsonl" ;;
-    host_once_prof)  # kernel stats of the host-direct Allreduce (page-locked callers), result once vs to every rank
-      run once_prof_on 200 bash -c "cd /tmp && MPJX_HOST_ONCE=1 MPJX_JNI_LATENCY_ONLY=pinned MPJX_JNI_LATENCY_CALLS=200 rocprofv3 --kernel-trace --stats --output-format csv -d '$OUT/${TAG}_once_prof_on' -o jni -- python3 '$R/tests/jni_driver.py' latency > '$OUT/${TAG}_once_prof_on.log' 2>&1" &&
-      run once_prof_off 200 bash -c "cd /tmp && MPJX_HOST_ONCE=0 MPJX_JNI_LATENCY_ONLY=pinned MPJX_JNI_LATENCY_CALLS=200 rocprofv3 --kernel-trace --stats --output-format csv -d '$OUT/${TAG}_once_prof_off' -o jni -- python3 '$R/tests/jni_driver.py' latency > '$OUT/${TAG}_once_prof_off.log' 2>&1" ;;
     probe_host) run build_probe_host 200 hipcc --offload-arch=gfx950 -O2 tools/probe_host_range.cpp -o /tmp/probe_host_range
                 run probe_host 60 bash -c "/tmp/probe_host_range > '$OUT/${TAG}_probe_host.jsonl' 2>&1"
                 cat "$OUT/${TAG}_probe_host.jsonl" ;;
