@@ -296,6 +296,45 @@ int mpjx_gather(mpjx_comm_t comm, const void *sendbuf, void *recvbuf, int64_t co
 int mpjx_scatter(mpjx_comm_t comm, const void *sendbuf, void *recvbuf, int64_t count, int type, int root,
                  void *stream);
 
+/* ---- block moves (Intracomm.Allgather .. Alltoallv, src/mpi/Intracomm.java:363-690) -----------------
+ * Device pointers; counts and displacements in ELEMENTS of `type` (a pair type's element is one pair),
+ * displacements from the start of the buffer they index, in any order, with gaps. The data is moved as
+ * plain bytes, so the calls take no flags and no byte order applies. Enqueued on `stream` and ordered
+ * like every other call. The buffers may sit at any byte alignment.
+ *   MPJX_ERR_ARG: a negative count or displacement, a NULL buffer or table with a nonzero count, an
+ *   unknown type, a bad root, a buffer that is not GPU-accessible, two receive segments of this rank
+ *   that overlap, or this rank's send and receive ranges overlapping (mpiJava has no in-place form).
+ * Count tables are significant where MPI says: recvcounts/displs of mpjx_gatherv and sendcounts/displs of
+ * mpjx_scatterv at the root only (as are recvbuf and sendbuf there).
+ * One rank, and multicore ranks sharing one device (MPJX_SMP_COPY unset): one launch of the block-move
+ * kernel for the whole world; there every rank sees every table, and a send count that differs from the
+ * matching receive count is MPJX_ERR_ARG on every rank before anything moves. In every other world
+ * (RCCL, HIP-IPC, multicore across devices, MPJX_SMP_COPY=1) the rank's own block is moved by that
+ * kernel and the rest by the transport's exchanges, and matching counts between ranks are the caller's
+ * contract, as in MPI. */
+/* Intracomm.Allgather: every rank's `count` elements land at recvbuf + r*count on every rank. */
+int mpjx_allgather(mpjx_comm_t comm, const void *sendbuf, void *recvbuf, int64_t count, int type,
+                   void *stream);
+/* Intracomm.Allgatherv: rank r's sendcount (= every rank's recvcounts[r]) elements land at
+ * recvbuf + displs[r] on every rank. */
+int mpjx_allgatherv(mpjx_comm_t comm, const void *sendbuf, int64_t sendcount, void *recvbuf,
+                    const int64_t *recvcounts, const int64_t *displs, int type, void *stream);
+/* Intracomm.Gatherv: rank r's sendcount elements land at recvbuf + displs[r] on the root. */
+int mpjx_gatherv(mpjx_comm_t comm, const void *sendbuf, int64_t sendcount, void *recvbuf,
+                 const int64_t *recvcounts, const int64_t *displs, int type, int root, void *stream);
+/* Intracomm.Scatterv: rank r receives sendcounts[r] (= its recvcount) elements from the root's
+ * sendbuf + displs[r]. */
+int mpjx_scatterv(mpjx_comm_t comm, const void *sendbuf, const int64_t *sendcounts, const int64_t *displs,
+                  void *recvbuf, int64_t recvcount, int type, int root, void *stream);
+/* Intracomm.Alltoall: block j (count elements at sendbuf + j*count) goes to rank j, which stores the
+ * block from rank i at recvbuf + i*count. */
+int mpjx_alltoall(mpjx_comm_t comm, const void *sendbuf, void *recvbuf, int64_t count, int type,
+                  void *stream);
+/* Intracomm.Alltoallv: sendcounts[j] elements at sendbuf + sdispls[j] go to rank j; recvcounts[i]
+ * elements from rank i land at recvbuf + rdispls[i]. */
+int mpjx_alltoallv(mpjx_comm_t comm, const void *sendbuf, const int64_t *sendcounts, const int64_t *sdispls,
+                   void *recvbuf, const int64_t *recvcounts, const int64_t *rdispls, int type, void *stream);
+
 /* ---- host-resident variants (Java heap arrays / mpjbuf payloads) ---------------------------------
  * Synchronous. Buffers are ordinary host memory; the library stages them through device memory.
  * These are what the JNI shim calls with GetPrimitiveArrayCritical / GetDirectBufferAddress

@@ -6,7 +6,9 @@
 //                                            src/mpi/Intracomm.java:740-760
 //   ::Allreduce / ::Reduce_scatter / ::Scan / ::Bcast / ::Barrier
 //                                            src/mpi/Intracomm.java:787-885
-//   mpi::MPIException                        src/mpi/MPIException.java:42 (unchecked, like the Java one)
+//   ::Allgather / ::Allgatherv / ::Gatherv / ::Scatterv / ::Alltoall / ::Alltoallv (device pointers, sendtype
+//   and recvtype as in mpiJava, which must be equal)   src/mpi/Intracomm.java:363-690
+//   mpi::MPIException                       src/mpi/MPIException.java:42 (unchecked, like the Java one)
 //   mpi::MPI::isOldSelected                  conf mpjexpress.mpi.old.collectives (src/mpi/MPI.java:70,266)
 // Buffers are typed pointers; offsets and counts are in elements. Device pointers take the device
 // path (blocking, like the Java calls); std::vector overloads are the host-resident path (the Java
@@ -153,6 +155,81 @@ class Intracomm {
     sync();
   }
 
+  // ---- block moves on device buffers (src/mpi/Intracomm.java:363-690): counts, displacements and
+  // offsets in elements; count tables significant where MPI says (mpjx.h) ----
+  template <class T>
+  void Allgather(const T* sendbuf, int sendoffset, int sendcount, const Datatype& sendtype, T* recvbuf,
+                 int recvoffset, int recvcount, const Datatype& recvtype) {
+    same_type<T>(sendtype, recvtype, "Allgather");
+    if (sendcount != recvcount) throw MPIException("Allgather: sendcount must equal recvcount");
+    check(mpjx_allgather(c_, sendbuf + sendoffset, recvbuf + recvoffset, sendcount, sendtype.code, nullptr),
+          "Allgather");
+    sync();
+  }
+  template <class T>
+  void Allgatherv(const T* sendbuf, int sendoffset, int sendcount, const Datatype& sendtype, T* recvbuf,
+                  int recvoffset, const std::vector<int>& recvcount, const std::vector<int>& displs,
+                  const Datatype& recvtype) {
+    same_type<T>(sendtype, recvtype, "Allgatherv");
+    std::vector<int64_t> rc = counts(recvcount), rd = counts(displs);
+    check(mpjx_allgatherv(c_, sendbuf + sendoffset, sendcount, recvbuf + recvoffset, rc.data(), rd.data(),
+                          sendtype.code, nullptr),
+          "Allgatherv");
+    sync();
+  }
+  template <class T>
+  void Gatherv(const T* sendbuf, int sendoffset, int sendcount, const Datatype& sendtype, T* recvbuf,
+               int recvoffset, const std::vector<int>& recvcount, const std::vector<int>& displs,
+               const Datatype& recvtype, int root) {
+    same_type<T>(sendtype, recvtype, "Gatherv");
+    std::vector<int64_t> rc, rd;
+    if (rank_ == root) {
+      rc = counts(recvcount);
+      rd = counts(displs);
+    }
+    check(mpjx_gatherv(c_, sendbuf + sendoffset, sendcount, rank_ == root ? recvbuf + recvoffset : nullptr,
+                       rank_ == root ? rc.data() : nullptr, rank_ == root ? rd.data() : nullptr, sendtype.code, root,
+                       nullptr),
+          "Gatherv");
+    sync();
+  }
+  template <class T>
+  void Scatterv(const T* sendbuf, int sendoffset, const std::vector<int>& sendcount, const std::vector<int>& displs,
+                const Datatype& sendtype, T* recvbuf, int recvoffset, int recvcount, const Datatype& recvtype,
+                int root) {
+    same_type<T>(sendtype, recvtype, "Scatterv");
+    std::vector<int64_t> sc, sd;
+    if (rank_ == root) {
+      sc = counts(sendcount);
+      sd = counts(displs);
+    }
+    check(mpjx_scatterv(c_, rank_ == root ? sendbuf + sendoffset : nullptr, rank_ == root ? sc.data() : nullptr,
+                        rank_ == root ? sd.data() : nullptr, recvbuf + recvoffset, recvcount, sendtype.code, root,
+                        nullptr),
+          "Scatterv");
+    sync();
+  }
+  template <class T>
+  void Alltoall(const T* sendbuf, int sendoffset, int sendcount, const Datatype& sendtype, T* recvbuf,
+                int recvoffset, int recvcount, const Datatype& recvtype) {
+    same_type<T>(sendtype, recvtype, "Alltoall");
+    if (sendcount != recvcount) throw MPIException("Alltoall: sendcount must equal recvcount");
+    check(mpjx_alltoall(c_, sendbuf + sendoffset, recvbuf + recvoffset, sendcount, sendtype.code, nullptr),
+          "Alltoall");
+    sync();
+  }
+  template <class T>
+  void Alltoallv(const T* sendbuf, int sendoffset, const std::vector<int>& sendcount,
+                 const std::vector<int>& sdispls, const Datatype& sendtype, T* recvbuf, int recvoffset,
+                 const std::vector<int>& recvcount, const std::vector<int>& rdispls, const Datatype& recvtype) {
+    same_type<T>(sendtype, recvtype, "Alltoallv");
+    std::vector<int64_t> sc = counts(sendcount), sd = counts(sdispls), rc = counts(recvcount), rd = counts(rdispls);
+    check(mpjx_alltoallv(c_, sendbuf + sendoffset, sc.data(), sd.data(), recvbuf + recvoffset, rc.data(), rd.data(),
+                         sendtype.code, nullptr),
+          "Alltoallv");
+    sync();
+  }
+
   // ---- host-resident arrays (the Java heap array case) ----
   template <class T>
   void Reduce(const std::vector<T>& sendbuf, int sendoffset, std::vector<T>& recvbuf, int recvoffset, int count,
@@ -210,6 +287,11 @@ class Intracomm {
   static void size_ok(const Datatype& dt) {
     if ((int)sizeof(T) != dt.byteSize)
       throw MPIException(std::string("buffer element size does not match MPI.") + dt.name);
+  }
+  template <class T>
+  static void same_type(const Datatype& sendtype, const Datatype& recvtype, const char* what) {
+    if (sendtype.code != recvtype.code) throw MPIException(std::string(what) + ": sendtype differs from recvtype");
+    size_ok<T>(sendtype);
   }
   template <class T>
   static void extent(const std::vector<T>& v, int off, int64_t count, int size = 1) {

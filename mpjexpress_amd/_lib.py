@@ -68,6 +68,12 @@ def _declare(L):
         "mpjx_bcast": ([vp, vp, c_i64, c_int, c_int, vp], c_int),
         "mpjx_gather": ([vp, vp, vp, c_i64, c_int, c_int, vp], c_int),
         "mpjx_scatter": ([vp, vp, vp, c_i64, c_int, c_int, vp], c_int),
+        "mpjx_allgather": ([vp, vp, vp, c_i64, c_int, vp], c_int),
+        "mpjx_allgatherv": ([vp, vp, c_i64, vp, pi64, pi64, c_int, vp], c_int),
+        "mpjx_gatherv": ([vp, vp, c_i64, vp, pi64, pi64, c_int, c_int, vp], c_int),
+        "mpjx_scatterv": ([vp, vp, pi64, pi64, vp, c_i64, c_int, c_int, vp], c_int),
+        "mpjx_alltoall": ([vp, vp, vp, c_i64, c_int, vp], c_int),
+        "mpjx_alltoallv": ([vp, vp, pi64, pi64, vp, pi64, pi64, c_int, vp], c_int),
         "mpjx_reduce_host": ([vp, vp, vp, c_i64, c_int, c_int, c_int, c_uint], c_int),
         "mpjx_allreduce_host": ([vp, vp, vp, c_i64, c_int, c_int, c_uint], c_int),
         "mpjx_reduce_scatter_host": ([vp, vp, vp, pi64, c_int, c_int, c_uint], c_int),

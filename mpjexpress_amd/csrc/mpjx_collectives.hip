@@ -1,6 +1,7 @@
 // mpjx_collectives.hip — the reduction collectives of libmpjx (Reduce, Allreduce, Reduce_scatter,
-// Scan), their companions (Bcast, Gather, Scatter), big-endian (mpjbuf) payload handling and the
-// host-resident variants, exported through the C ABI declared in include/mpjx.h.
+// Scan), their companions (Bcast, Gather, Scatter), the block moves (Allgather(v), Gatherv, Scatterv,
+// Alltoall(v)), big-endian (mpjbuf) payload handling and the host-resident variants, exported through
+// the C ABI declared in include/mpjx.h.
 //
 // Reference behaviour followed (file:line in /root/reference):
 //   Reduce          src/mpi/PureIntracomm.java:1923-1992 (MST_Reduce), :1994-2057 (FT_Reduce)
@@ -1599,6 +1600,206 @@ extern "C" int mpjx_comm_last_host_form(mpjx_comm_t c, int* form) {
   return MPJX_SUCCESS;
 }
 
+// ---------------------------------------------------------------------------------------------
+// block moves: Allgather, Allgatherv, Gatherv, Scatterv, Alltoall, Alltoallv
+// (src/mpi/Intracomm.java:363-690 -> PureIntracomm.java). Plain bytes: no op, no byte order. Each call
+// is, per rank, P send ranges (S[j]: what goes to rank j) and P receive ranges (R[j]: what comes from
+// rank j) in bytes from its two buffers (planned and validated by mpjx_moves_plan.hpp), then one of
+// three engines:
+//   P = 1                     one k_moves launch (never hipMemcpyAsync)
+//   multicore, one device     every rank publishes its buffers and ranges (share), rank 0 launches
+//                             k_moves over the whole world's <= P x P segments, every rank fences: one
+//                             kernel and two rendezvous per call, like the reductions. Every rank sees
+//                             every table there, so a send length that differs from the matching
+//                             receive length is MPJX_ERR_ARG on every rank before any launch.
+//   every other world         the rank's own block by k_moves, the rest through the transport
+//                             (allgather_equal / alltoallv / exchange), where matching counts are the
+//                             caller's contract as in MPI. Multicore ranks on distinct devices take this
+//                             path too: a one-launch kernel over peer memory has no machine to be tested on.
+
+namespace {
+
+struct MovePlan {
+  const char* send;
+  char* recv;
+  std::vector<ByteRange> S, R;
+};
+
+enum MoveKind { MV_ALLGATHER, MV_ALLTOALL, MV_EXCHANGE };
+
+int plan_fail(const std::string& err) { return fail(MPJX_ERR_ARG, "%s", err.c_str()); }
+
+// p->X[at] = `count` elements at offset 0, every other entry empty (n entries)
+int plan_single(std::vector<ByteRange>* x, int n, int at, int64_t count, int esz, const char* what) {
+  std::vector<ByteRange> one;
+  std::string err;
+  if (!plan_ranges(&count, nullptr, 1, esz, &one, &err, what)) return plan_fail(err);
+  x->assign((size_t)n, ByteRange{0, 0});
+  if (at >= 0) (*x)[(size_t)at] = one[0];
+  else x->assign((size_t)n, one[0]);  // at < 0: the same range for every rank
+  return MPJX_SUCCESS;
+}
+
+int plan_table(std::vector<ByteRange>* x, int n, const int64_t* counts, const int64_t* displs, int esz,
+               const char* what) {
+  if (!counts || !displs) return fail(MPJX_ERR_ARG, "%s or their displacements are NULL", what);
+  std::string err;
+  if (!plan_ranges(counts, displs, n, esz, x, &err, what)) return plan_fail(err);
+  return MPJX_SUCCESS;
+}
+
+int moves_check(mpjx_comm* c, const MovePlan& p) {
+  int64_t st = 0, rt = 0;
+  for (const ByteRange& x : p.S) st += x.len;
+  for (const ByteRange& x : p.R) rt += x.len;
+  if ((st > 0 && !p.send) || (rt > 0 && !p.recv)) return fail(MPJX_ERR_ARG, "NULL buffer with a nonzero count");
+  CHK(check_bufs(c, st > 0 ? p.send : nullptr, rt > 0 ? p.recv : nullptr));
+  int a = 0, b = 0;
+  if (ranges_overlap(p.R, &a, &b))
+    return fail(MPJX_ERR_ARG, "the receive segments from ranks %d and %d overlap", a, b);
+  if (ranges_cross((uint64_t)(uintptr_t)p.send, p.S, (uint64_t)(uintptr_t)p.recv, p.R))
+    return fail(MPJX_ERR_ARG, "send and receive ranges overlap (these collectives have no in-place form)");
+  return MPJX_SUCCESS;
+}
+
+int own_mismatch(int me, const MovePlan& p) {
+  return fail(MPJX_ERR_ARG, "rank %d sends itself %lld bytes but receives %lld", me, (long long)p.S[me].len,
+              (long long)p.R[me].len);
+}
+
+int moves_run(mpjx_comm* c, MoveKind kind, MovePlan& p, int type, void* stream) {
+  CHK(moves_check(c, p));
+  Call k;
+  CHK(k.begin(c, stream, type));
+  const int P = c->size, me = c->rank;
+  if (p.S[me].len != p.R[me].len) return own_mismatch(me, p);
+  auto* t = dynamic_cast<SmpTransport*>(c->tr.get());
+  if (P > 1 && t && smp_direct(c) && t->single()) {
+    // The ranges stay in this rank's frame: no rank leaves the call before the fence's rendezvous
+    std::vector<std::vector<const void*>> all;
+    CHK(t->share(std::vector<const void*>{p.send, p.recv, &p.S, &p.R}, k.s, &all, true));
+    auto S = [&](int i) -> const std::vector<ByteRange>& { return *(const std::vector<ByteRange>*)all[i][2]; };
+    auto R = [&](int i) -> const std::vector<ByteRange>& { return *(const std::vector<ByteRange>*)all[i][3]; };
+    for (int i = 0; i < P; i++)
+      for (int j = 0; j < P; j++)
+        if (S(i)[j].len != R(j)[i].len) {
+          const long long sl = S(i)[j].len, rl = R(j)[i].len;
+          (void)t->fence(k.s, true);  // every rank has read every table before any rank returns
+          return fail(MPJX_ERR_ARG, "rank %d sends %lld bytes to rank %d, which receives %lld", i, sl, j, rl);
+        }
+    if (me == 0) {
+      MoveList ml;
+      for (int j = 0; j < P; j++)    // receiver
+        for (int i = 0; i < P; i++)  // sender
+          ml.add((char*)all[j][1] + R(j)[i].off, (const char*)all[i][0] + S(i)[j].off, R(j)[i].len);
+      HIPCHK(launch_moves(ml, k.s));
+    }
+    CHK(t->fence(k.s, true));
+    return k.end();
+  }
+  {
+    MoveList ml;
+    ml.add(p.recv + p.R[me].off, p.send + p.S[me].off, p.R[me].len);
+    HIPCHK(launch_moves(ml, k.s));
+  }
+  if (P == 1) return k.end();
+  if (kind == MV_ALLGATHER) {
+    CHK(c->tr->allgather_equal(me, P, p.recv, (size_t)p.R[me].len, k.s));
+  } else if (kind == MV_ALLTOALL) {
+    std::vector<size_t> sc(P), sd(P), rc(P), rd(P);
+    for (int j = 0; j < P; j++) {
+      sc[j] = j == me ? 0 : (size_t)p.S[j].len;
+      sd[j] = (size_t)p.S[j].off;
+      rc[j] = j == me ? 0 : (size_t)p.R[j].len;
+      rd[j] = (size_t)p.R[j].off;
+    }
+    CHK(c->tr->alltoallv(me, p.send, sc, sd, p.recv, rc, rd, k.s));
+  } else {
+    std::vector<Xfer> sends, recvs;
+    for (int j = 0; j < P; j++) {
+      if (j == me) continue;
+      if (p.S[j].len > 0) sends.push_back({j, (void*)(p.send + p.S[j].off), (size_t)p.S[j].len});
+      if (p.R[j].len > 0) recvs.push_back({j, p.recv + p.R[j].off, (size_t)p.R[j].len});
+    }
+    CHK(c->tr->exchange(sends, recvs, k.s));
+  }
+  return k.end();
+}
+
+int moves_begin(mpjx_comm* c, int type, int* esz) {
+  if (!c) return fail(MPJX_ERR_ARG, "comm is NULL");
+  *esz = mpjx_type_size(type);
+  if (*esz == 0) return fail(MPJX_ERR_ARG, "unknown datatype code %d", type);
+  return MPJX_SUCCESS;
+}
+
+}  // namespace
+
+static int allgather_entry(mpjx_comm_t c, const void* sendbuf, void* recvbuf, int64_t count, int type, void* stream) {
+  int esz;
+  CHK(moves_begin(c, type, &esz));
+  MovePlan p{(const char*)sendbuf, (char*)recvbuf, {}, {}};
+  std::string err;
+  if (!plan_equal(count, c->size, esz, &p.R, &err)) return plan_fail(err);
+  CHK(plan_single(&p.S, c->size, -1, count, esz, "count"));
+  return moves_run(c, MV_ALLGATHER, p, type, stream);
+}
+
+static int allgatherv_entry(mpjx_comm_t c, const void* sendbuf, int64_t sendcount, void* recvbuf,
+                            const int64_t* recvcounts, const int64_t* displs, int type, void* stream) {
+  int esz;
+  CHK(moves_begin(c, type, &esz));
+  MovePlan p{(const char*)sendbuf, (char*)recvbuf, {}, {}};
+  CHK(plan_table(&p.R, c->size, recvcounts, displs, esz, "recvcounts"));
+  CHK(plan_single(&p.S, c->size, -1, sendcount, esz, "sendcount"));
+  return moves_run(c, MV_EXCHANGE, p, type, stream);
+}
+
+static int gatherv_entry(mpjx_comm_t c, const void* sendbuf, int64_t sendcount, void* recvbuf,
+                         const int64_t* recvcounts, const int64_t* displs, int type, int root, void* stream) {
+  int esz;
+  CHK(moves_begin(c, type, &esz));
+  CHK(check_root(c, root));
+  MovePlan p{(const char*)sendbuf, (char*)recvbuf, {}, {}};
+  if (c->rank == root) CHK(plan_table(&p.R, c->size, recvcounts, displs, esz, "recvcounts"));
+  else p.R.assign((size_t)c->size, ByteRange{0, 0});
+  CHK(plan_single(&p.S, c->size, root, sendcount, esz, "sendcount"));
+  return moves_run(c, MV_EXCHANGE, p, type, stream);
+}
+
+static int scatterv_entry(mpjx_comm_t c, const void* sendbuf, const int64_t* sendcounts, const int64_t* displs,
+                          void* recvbuf, int64_t recvcount, int type, int root, void* stream) {
+  int esz;
+  CHK(moves_begin(c, type, &esz));
+  CHK(check_root(c, root));
+  MovePlan p{(const char*)sendbuf, (char*)recvbuf, {}, {}};
+  if (c->rank == root) CHK(plan_table(&p.S, c->size, sendcounts, displs, esz, "sendcounts"));
+  else p.S.assign((size_t)c->size, ByteRange{0, 0});
+  CHK(plan_single(&p.R, c->size, root, recvcount, esz, "recvcount"));
+  return moves_run(c, MV_EXCHANGE, p, type, stream);
+}
+
+static int alltoall_entry(mpjx_comm_t c, const void* sendbuf, void* recvbuf, int64_t count, int type, void* stream) {
+  int esz;
+  CHK(moves_begin(c, type, &esz));
+  MovePlan p{(const char*)sendbuf, (char*)recvbuf, {}, {}};
+  std::string err;
+  if (!plan_equal(count, c->size, esz, &p.S, &err)) return plan_fail(err);
+  p.R = p.S;
+  return moves_run(c, MV_ALLTOALL, p, type, stream);
+}
+
+static int alltoallv_entry(mpjx_comm_t c, const void* sendbuf, const int64_t* sendcounts, const int64_t* sdispls,
+                           void* recvbuf, const int64_t* recvcounts, const int64_t* rdispls, int type,
+                           void* stream) {
+  int esz;
+  CHK(moves_begin(c, type, &esz));
+  MovePlan p{(const char*)sendbuf, (char*)recvbuf, {}, {}};
+  CHK(plan_table(&p.S, c->size, sendcounts, sdispls, esz, "sendcounts"));
+  CHK(plan_table(&p.R, c->size, recvcounts, rdispls, esz, "recvcounts"));
+  return moves_run(c, MV_ALLTOALL, p, type, stream);
+}
+
 // The C-ABI entry points. A call that fails leaves this rank out of step with its peers (it skipped the
 // collective, or stopped between two of its transport steps): `ended` tells the transport
 // (Transport::call_failed). Multicore and IPC worlds are marked failed, so peers waiting for this rank
@@ -1622,6 +1823,37 @@ extern "C" int mpjx_gather(mpjx_comm_t c, const void* sendbuf, void* recvbuf, in
 extern "C" int mpjx_scatter(mpjx_comm_t c, const void* sendbuf, void* recvbuf, int64_t count, int type, int root,
                             void* stream) {
   return ended(c, scatter_entry(c, sendbuf, recvbuf, count, type, root, stream));
+}
+
+extern "C" int mpjx_allgather(mpjx_comm_t c, const void* sendbuf, void* recvbuf, int64_t count, int type,
+                              void* stream) {
+  return ended(c, allgather_entry(c, sendbuf, recvbuf, count, type, stream));
+}
+
+extern "C" int mpjx_allgatherv(mpjx_comm_t c, const void* sendbuf, int64_t sendcount, void* recvbuf,
+                               const int64_t* recvcounts, const int64_t* displs, int type, void* stream) {
+  return ended(c, allgatherv_entry(c, sendbuf, sendcount, recvbuf, recvcounts, displs, type, stream));
+}
+
+extern "C" int mpjx_gatherv(mpjx_comm_t c, const void* sendbuf, int64_t sendcount, void* recvbuf,
+                            const int64_t* recvcounts, const int64_t* displs, int type, int root, void* stream) {
+  return ended(c, gatherv_entry(c, sendbuf, sendcount, recvbuf, recvcounts, displs, type, root, stream));
+}
+
+extern "C" int mpjx_scatterv(mpjx_comm_t c, const void* sendbuf, const int64_t* sendcounts, const int64_t* displs,
+                             void* recvbuf, int64_t recvcount, int type, int root, void* stream) {
+  return ended(c, scatterv_entry(c, sendbuf, sendcounts, displs, recvbuf, recvcount, type, root, stream));
+}
+
+extern "C" int mpjx_alltoall(mpjx_comm_t c, const void* sendbuf, void* recvbuf, int64_t count, int type,
+                             void* stream) {
+  return ended(c, alltoall_entry(c, sendbuf, recvbuf, count, type, stream));
+}
+
+extern "C" int mpjx_alltoallv(mpjx_comm_t c, const void* sendbuf, const int64_t* sendcounts, const int64_t* sdispls,
+                              void* recvbuf, const int64_t* recvcounts, const int64_t* rdispls, int type,
+                              void* stream) {
+  return ended(c, alltoallv_entry(c, sendbuf, sendcounts, sdispls, recvbuf, recvcounts, rdispls, type, stream));
 }
 
 extern "C" int mpjx_allreduce(mpjx_comm_t c, const void* sendbuf, void* recvbuf, int64_t count, int type, int op,

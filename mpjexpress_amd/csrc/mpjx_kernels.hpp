@@ -28,6 +28,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "mpjx_moves_plan.hpp"
 #include "mpjx_ops.hpp"
 
 namespace mpjx {
@@ -630,6 +631,18 @@ struct CopyList {
   }
 };
 hipError_t launch_copies(const CopyList& l, hipStream_t s);
+
+// Any number of independent device moves with any (src mod 16, dst mod 16) pair and ragged lengths
+// (mpjx_k_moves.hip): the block-move collectives' segments. Empty segments are dropped here; more than
+// one table's worth (kMoveMax, mpjx_moves_plan.hpp) runs as consecutive launches on the stream. Source
+// and destination segments must not overlap each other.
+struct MoveList {
+  std::vector<MoveSeg> segs;
+  void add(void* d, const void* s_, int64_t b) {
+    if (b > 0) segs.push_back(MoveSeg{(uint64_t)(uintptr_t)s_, (uint64_t)(uintptr_t)d, b});
+  }
+};
+hipError_t launch_moves(const MoveList& l, hipStream_t s);
 
 // IPC device sync (mpjx_ipc.hip): flag slots of the peers (peer[j] = peer j's slot for this rank),
 // this rank's own slots, and the bounded wait's limits; counter = a zeroed device word for the

@@ -9,6 +9,9 @@ reference's own programs (e.g. test/mpi/ccl/allreduce.java):
     comm.Reduce_scatter(send, soff, recv, roff, recvcounts, datatype, op) src/mpi/Intracomm.java:833-840
     comm.Scan(send, soff, recv, roff, count, datatype, op)               src/mpi/Intracomm.java:879-885
     comm.Bcast(buf, off, count, datatype, root), comm.Barrier(), comm.Rank(), comm.Size()
+    comm.Allgather / Allgatherv / Gatherv / Scatterv / Alltoall / Alltoallv(sendbuf, sendoffset, sendcount[s],
+        [sdispls,] sendtype, recvbuf, recvoffset, recvcount[s], [rdispls,] recvtype[, root])
+                                                 src/mpi/Intracomm.java:363-690 (device tensors only)
 
 Buffers are device-resident torch tensors (the device path) or numpy arrays (the host-resident
 path, as Java heap arrays are). Offsets and counts are in elements. Calls block until the result is
@@ -354,6 +357,89 @@ class Intracomm:
 
     def Scatter(self, sendbuf, sendoffset, sendcount, recvbuf, recvoffset, recvcount, datatype, root):
         Scatter(self, sendbuf, sendoffset, sendcount, recvbuf, recvoffset, recvcount, datatype, root)
+
+    # -- block moves (src/mpi/Intracomm.java:363-690): device tensors; counts, displacements and offsets
+    # in elements. One k_moves launch at P = 1 and in one-device multicore worlds, the transport's
+    # exchanges elsewhere (include/mpjx.h).
+    def _moves(self, name, sendbuf, sendtype, recvbuf, recvtype):
+        if sendtype is not recvtype and sendtype.code != recvtype.code:
+            raise MPIException(f"{name}: sendtype {sendtype} differs from recvtype {recvtype}")
+        for b in (sendbuf, recvbuf):
+            if b is not None and not _is_torch(b):
+                raise MPIException(f"{name} is provided for device-resident buffers")
+        self._sync_in(*(b for b in (sendbuf, recvbuf) if b is not None))
+
+    def _table(self, name, counts, displs):
+        """(counts, displs as int64 arrays, elements spanned) of one rank's count/displacement lists."""
+        c, d = [int(x) for x in counts][: self._size], [int(x) for x in displs][: self._size]
+        if len(c) < self._size or len(d) < self._size:
+            raise MPIException(f"{name}: counts or displacements shorter than the communicator")
+        span = max([dj + cj for cj, dj in zip(c, d) if cj > 0] or [0])
+        arr = ctypes.c_int64 * self._size
+        return arr(*c), arr(*d), span
+
+    def Allgather(self, sendbuf, sendoffset, sendcount, sendtype, recvbuf, recvoffset, recvcount, recvtype):
+        self._moves("Allgather", sendbuf, sendtype, recvbuf, recvtype)
+        if sendcount != recvcount:
+            raise MPIException("Allgather: sendcount must equal recvcount")
+        sp = _dev_ptr(sendbuf, sendoffset, sendtype, sendcount)
+        rp = _dev_ptr(recvbuf, recvoffset, recvtype, recvcount * self._size)
+        _wrap("mpjx_allgather", self._h, sp, rp, sendcount, sendtype.code, None)
+        self._sync_out()
+
+    def Allgatherv(self, sendbuf, sendoffset, sendcount, sendtype, recvbuf, recvoffset, recvcount, displs,
+                   recvtype):
+        self._moves("Allgatherv", sendbuf, sendtype, recvbuf, recvtype)
+        rc, rd, span = self._table("Allgatherv", recvcount, displs)
+        sp = _dev_ptr(sendbuf, sendoffset, sendtype, sendcount)
+        rp = _dev_ptr(recvbuf, recvoffset, recvtype, span)
+        _wrap("mpjx_allgatherv", self._h, sp, sendcount, rp, rc, rd, sendtype.code, None)
+        self._sync_out()
+
+    def Gatherv(self, sendbuf, sendoffset, sendcount, sendtype, recvbuf, recvoffset, recvcount, displs,
+                recvtype, root):
+        """recvbuf, recvcount and displs are significant at the root only."""
+        is_root = self._rank == root
+        self._moves("Gatherv", sendbuf, sendtype, recvbuf if is_root else None, recvtype)
+        rc = rd = rp = None
+        if is_root:
+            rc, rd, span = self._table("Gatherv", recvcount, displs)
+            rp = _dev_ptr(recvbuf, recvoffset, recvtype, span)
+        sp = _dev_ptr(sendbuf, sendoffset, sendtype, sendcount)
+        _wrap("mpjx_gatherv", self._h, sp, sendcount, rp, rc, rd, sendtype.code, root, None)
+        self._sync_out()
+
+    def Scatterv(self, sendbuf, sendoffset, sendcount, displs, sendtype, recvbuf, recvoffset, recvcount,
+                 recvtype, root):
+        """sendbuf, sendcount and displs are significant at the root only."""
+        is_root = self._rank == root
+        self._moves("Scatterv", sendbuf if is_root else None, sendtype, recvbuf, recvtype)
+        sc = sd = sp = None
+        if is_root:
+            sc, sd, span = self._table("Scatterv", sendcount, displs)
+            sp = _dev_ptr(sendbuf, sendoffset, sendtype, span)
+        rp = _dev_ptr(recvbuf, recvoffset, recvtype, recvcount)
+        _wrap("mpjx_scatterv", self._h, sp, sc, sd, rp, recvcount, sendtype.code, root, None)
+        self._sync_out()
+
+    def Alltoall(self, sendbuf, sendoffset, sendcount, sendtype, recvbuf, recvoffset, recvcount, recvtype):
+        self._moves("Alltoall", sendbuf, sendtype, recvbuf, recvtype)
+        if sendcount != recvcount:
+            raise MPIException("Alltoall: sendcount must equal recvcount")
+        sp = _dev_ptr(sendbuf, sendoffset, sendtype, sendcount * self._size)
+        rp = _dev_ptr(recvbuf, recvoffset, recvtype, recvcount * self._size)
+        _wrap("mpjx_alltoall", self._h, sp, rp, sendcount, sendtype.code, None)
+        self._sync_out()
+
+    def Alltoallv(self, sendbuf, sendoffset, sendcount, sdispls, sendtype, recvbuf, recvoffset, recvcount,
+                  rdispls, recvtype):
+        self._moves("Alltoallv", sendbuf, sendtype, recvbuf, recvtype)
+        sc, sd, sspan = self._table("Alltoallv", sendcount, sdispls)
+        rc, rd, rspan = self._table("Alltoallv", recvcount, rdispls)
+        sp = _dev_ptr(sendbuf, sendoffset, sendtype, sspan)
+        rp = _dev_ptr(recvbuf, recvoffset, recvtype, rspan)
+        _wrap("mpjx_alltoallv", self._h, sp, sc, sd, rp, rc, rd, sendtype.code, None)
+        self._sync_out()
 
     def Bcast(self, buf, offset, count, datatype, root):
         if not _is_torch(buf):
