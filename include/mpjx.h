@@ -335,6 +335,55 @@ int mpjx_alltoall(mpjx_comm_t comm, const void *sendbuf, void *recvbuf, int64_t 
 int mpjx_alltoallv(mpjx_comm_t comm, const void *sendbuf, const int64_t *sendcounts, const int64_t *sdispls,
                    void *recvbuf, const int64_t *recvcounts, const int64_t *rdispls, int type, void *stream);
 
+/* ---- derived datatypes and the strided block move (src/mpi/Contiguous.java, src/mpi/Vector.java) -------
+ * A derived type normalises to `nblocks` blocks of `blocklen` elements of its basic type, `stride` elements
+ * apart: size = nblocks*blocklen, extent = (nblocks-1)*stride + blocklen (0 for an empty type, as
+ * Vector.computeBounds gives for a positive stride), lb = 0. `oldtype` is a basic code, a pair code (which is
+ * Contiguous(2, base)) or a derived code that is itself contiguous; stride is in units of oldtype's extent.
+ * Vector(c, b, b, T), count <= 1 and an empty block normalise to contiguous.
+ *   MPJX_ERR_ARG: a negative count or blocklength, an unknown or freed oldtype, sizes beyond 2^62 bytes.
+ *   MPJX_ERR_UNSUPPORTED (the message names what was passed): a stride smaller than the block length
+ *   (negative, zero or overlapping), a strided oldtype (Vector of Vector, Contiguous of Vector).
+ * Hvector, Indexed, Hindexed, Struct and the LB/UB markers are not provided.
+ * Derived codes are handles >= 0x10000 from a process-wide, thread-safe registry, local to the rank as MPI
+ * types are (only the signatures must match between ranks). A freed code is never reissued; a freed or
+ * unknown code is MPJX_ERR_ARG in every later call. mpjx_type_size() returns 0 for a derived code, so every
+ * entry point above rejects one as an unknown datatype; mpjx_type_info is the authority for them (and
+ * answers basic and pair codes too: base = the basic code, size and extent in its elements). */
+int mpjx_type_contiguous(int64_t count, int oldtype, int *newtype);
+int mpjx_type_vector(int64_t count, int64_t blocklength, int64_t stride, int oldtype, int *newtype);
+int mpjx_type_free(int type);
+int mpjx_type_info(int type, int *base, int64_t *size, int64_t *extent);
+/* The general block move: sendcounts[j] items of sendtype, the first at sendbuf + sdispls[j], go to rank j;
+ * recvcounts[i] items of recvtype from rank i land from recvbuf + rdispls[i]. Every block move and every
+ * rooted call is a special case, with zero counts where a rank has nothing to send or receive.
+ * Counts are ITEMS of the side's type; item k of a message lies k extents after the first. Displacements are
+ * in elements of the BASIC type, as the reference's v-calls add them to the buffer offset
+ * (PureIntracomm.java:984,1232,1630,1832,1848): Alltoallv with a Vector send type is a transpose without a
+ * resized type. A message's packed form is its blocks in order; a send matches a receive when both types have
+ * the same basic type and the packed lengths are equal, and the packed bytes are stored in order into the
+ * receive layout (the block shapes need not agree). Only bytes inside receive blocks are written.
+ *   MPJX_ERR_ARG: as for the block moves above, an unknown or freed type, types of different basic types,
+ *   two receive layouts of this rank that share a byte, or a send layout that shares a byte with a receive
+ *   layout. That check is exact (two interleaved columns of one matrix do not overlap): layouts whose
+ *   bounding spans are disjoint are settled at any size; where spans meet, the blocks are compared while the
+ *   call's tables hold at most 65,536 blocks in total; beyond that it is skipped and disjoint layouts are
+ *   the caller's contract, as in MPI.
+ *   MPJX_ERR_UNSUPPORTED: one message of 2^32 or more granules (the largest power of two <= 16 B that divides
+ *   both layouts' block bytes, strides, extents and addresses).
+ * No flags and no faithful mode. Enqueued on `stream`, ordered and failure-marked like the other collectives.
+ * A segment whose two layouts are contiguous runs the block-move kernel, every other one the strided kernel.
+ * One rank, and multicore ranks sharing one device (MPJX_SMP_COPY unset): one launch per kernel for the whole
+ * world; a base-type or packed-length mismatch between a sender and its receiver is MPJX_ERR_ARG on every
+ * rank before anything moves. In every other world the rank's own block moves from layout to layout, strided
+ * sends are packed into communicator scratch, the packed bytes go through the transport's exchange and
+ * strided receives are unpacked; a contiguous side is sent from, or received into, its buffer, and matching
+ * signatures are the caller's contract. */
+int mpjx_alltoallv_dt(mpjx_comm_t comm,
+                      const void *sendbuf, const int64_t *sendcounts, const int64_t *sdispls, int sendtype,
+                      void *recvbuf, const int64_t *recvcounts, const int64_t *rdispls, int recvtype,
+                      void *stream);
+
 /* ---- host-resident variants (Java heap arrays / mpjbuf payloads) ---------------------------------
  * Synchronous. Buffers are ordinary host memory; the library stages them through device memory.
  * These are what the JNI shim calls with GetPrimitiveArrayCritical / GetDirectBufferAddress

@@ -7,7 +7,11 @@
 //   ::Allreduce / ::Reduce_scatter / ::Scan / ::Bcast / ::Barrier
 //                                            src/mpi/Intracomm.java:787-885
 //   ::Allgather / ::Allgatherv / ::Gatherv / ::Scatterv / ::Alltoall / ::Alltoallv (device pointers, sendtype
-//   and recvtype as in mpiJava, which must be equal)   src/mpi/Intracomm.java:363-690
+//   and recvtype as in mpiJava, of one base type)      src/mpi/Intracomm.java:363-690
+//   mpi::Datatype::Contiguous / ::Vector      src/mpi/Contiguous.java, src/mpi/Vector.java: with a derived type
+//   on either side (or two different types of one base type) the nine data-movement calls build the tables of
+//   mpjx_alltoallv_dt: counts in items, v-call displacements in base elements, block j of an equal-count
+//   call j * count extents into the buffer (mpjx.h)
 //   mpi::MPIException                       src/mpi/MPIException.java:42 (unchecked, like the Java one)
 //   mpi::MPI::isOldSelected                  conf mpjexpress.mpi.old.collectives (src/mpi/MPI.java:70,266)
 // Buffers are typed pointers; offsets and counts are in elements. Device pointers take the device
@@ -15,6 +19,8 @@
 // heap array case). Header-only: link libmpjx.
 #pragma once
 #include <mpjx.h>
+
+#include <stdint.h>
 
 #include <stdexcept>
 #include <string>
@@ -35,12 +41,48 @@ inline void check(int status, const char* what) {
 // A basic type, or a (value, index) pair type SHORT2..DOUBLE2 = Contiguous(2, base)
 // (src/mpi/MPI.java:110-114): `code` crosses the C ABI; buffers are arrays of the base type,
 // offsets are base-element indices, counts are datatype elements (pairs).
+// A derived type (Contiguous, Vector) owns a code of the library's registry until Free(), as in mpiJava;
+// copies share it.
 struct Datatype {
   int code;
   int byteSize;  // bytes of the base type
   const char* name;
-  int size = 1;
+  int size = 1;      // base elements of data per item
+  int extent = 0;    // base elements from one item to the next (0: size)
+  int base = 0;      // the basic type's code (0: code & 0xff)
+  bool derived = false;
   int Size() const { return size; }
+  int Extent() const { return extent ? extent : size; }
+  int Lb() const { return 0; }
+  int Ub() const { return Extent(); }
+  int Base() const { return base ? base : (code & 0xff); }
+  void Commit() const {}
+  void Free() {
+    if (!derived) return;
+    check(mpjx_type_free(code), "Datatype.Free");
+    derived = false;
+  }
+  static Datatype Contiguous(int count, const Datatype& oldtype) {
+    int code = 0;
+    check(mpjx_type_contiguous(count, oldtype.code, &code), "Datatype.Contiguous");
+    return made(code, oldtype, "Contiguous");
+  }
+  static Datatype Vector(int count, int blocklength, int stride, const Datatype& oldtype) {
+    int code = 0;
+    check(mpjx_type_vector(count, blocklength, stride, oldtype.code, &code), "Datatype.Vector");
+    return made(code, oldtype, "Vector");
+  }
+  // the Datatype of a code the library handed out
+  static Datatype made(int code, const Datatype& oldtype, const char* name) {
+    int base = 0;
+    int64_t size = 0, extent = 0;
+    check(mpjx_type_info(code, &base, &size, &extent), "mpjx_type_info");
+    if (size > INT32_MAX || extent > INT32_MAX) {
+      (void)mpjx_type_free(code);
+      throw MPIException(std::string(name) + ": the type exceeds this mirror's int sizes");
+    }
+    return Datatype{code, oldtype.byteSize, name, (int)size, (int)extent, base, true};
+  }
 };
 
 struct Op {
@@ -130,6 +172,13 @@ class Intracomm {
   template <class T>
   void Bcast(T* buf, int offset, int count, const Datatype& dt, int root) {
     size_ok<T>(dt);
+    if (dt.derived) {  // the root sends to every other rank; its own entry stays empty (the same bytes)
+      std::vector<int64_t> z(size_, 0), sc(size_, rank_ == root ? count : 0), rc(size_, 0);
+      sc[root] = 0;
+      if (rank_ != root) rc[root] = count;
+      return dt_move("Bcast", rank_ == root ? buf + offset : nullptr, sc, z, dt, rank_ == root ? nullptr : buf + offset,
+                     rc, z, dt);
+    }
     check(mpjx_bcast(c_, buf + offset, count, dt.code, root, nullptr), "Bcast");
     sync();
   }
@@ -139,6 +188,12 @@ class Intracomm {
               const Datatype& dt, int root) {
     size_ok<T>(dt);
     if (sendcount != recvcount) throw MPIException("Gather: sendcount must equal recvcount");
+    if (dt.derived) {
+      std::vector<int64_t> z(size_, 0), sc(size_, 0), rc(size_, rank_ == root ? recvcount : 0);
+      sc[root] = sendcount;
+      return dt_move("Gather", sendbuf + sendoffset, sc, z, dt, rank_ == root ? recvbuf + recvoffset : nullptr, rc,
+                     rank_ == root ? blocks(recvcount, dt) : z, dt);
+    }
     check(mpjx_gather(c_, sendbuf + sendoffset, rank_ == root ? recvbuf + recvoffset : nullptr, sendcount, dt.code,
                       root, nullptr),
           "Gather");
@@ -149,6 +204,12 @@ class Intracomm {
                const Datatype& dt, int root) {
     size_ok<T>(dt);
     if (sendcount != recvcount) throw MPIException("Scatter: sendcount must equal recvcount");
+    if (dt.derived) {
+      std::vector<int64_t> z(size_, 0), sc(size_, rank_ == root ? sendcount : 0), rc(size_, 0);
+      rc[root] = recvcount;
+      return dt_move("Scatter", rank_ == root ? sendbuf + sendoffset : nullptr, sc,
+                     rank_ == root ? blocks(sendcount, dt) : z, dt, recvbuf + recvoffset, rc, z, dt);
+    }
     check(mpjx_scatter(c_, rank_ == root ? sendbuf + sendoffset : nullptr, recvbuf + recvoffset, recvcount, dt.code,
                        root, nullptr),
           "Scatter");
@@ -160,7 +221,12 @@ class Intracomm {
   template <class T>
   void Allgather(const T* sendbuf, int sendoffset, int sendcount, const Datatype& sendtype, T* recvbuf,
                  int recvoffset, int recvcount, const Datatype& recvtype) {
-    same_type<T>(sendtype, recvtype, "Allgather");
+    if (strided<T>(sendtype, recvtype, "Allgather")) {
+      equal_length("Allgather", sendcount, sendtype, recvcount, recvtype);
+      return dt_move("Allgather", sendbuf + sendoffset, std::vector<int64_t>(size_, sendcount),
+                     std::vector<int64_t>(size_, 0), sendtype, recvbuf + recvoffset,
+                     std::vector<int64_t>(size_, recvcount), blocks(recvcount, recvtype), recvtype);
+    }
     if (sendcount != recvcount) throw MPIException("Allgather: sendcount must equal recvcount");
     check(mpjx_allgather(c_, sendbuf + sendoffset, recvbuf + recvoffset, sendcount, sendtype.code, nullptr),
           "Allgather");
@@ -170,8 +236,10 @@ class Intracomm {
   void Allgatherv(const T* sendbuf, int sendoffset, int sendcount, const Datatype& sendtype, T* recvbuf,
                   int recvoffset, const std::vector<int>& recvcount, const std::vector<int>& displs,
                   const Datatype& recvtype) {
-    same_type<T>(sendtype, recvtype, "Allgatherv");
     std::vector<int64_t> rc = counts(recvcount), rd = counts(displs);
+    if (strided<T>(sendtype, recvtype, "Allgatherv"))
+      return dt_move("Allgatherv", sendbuf + sendoffset, std::vector<int64_t>(size_, sendcount),
+                     std::vector<int64_t>(size_, 0), sendtype, recvbuf + recvoffset, rc, rd, recvtype);
     check(mpjx_allgatherv(c_, sendbuf + sendoffset, sendcount, recvbuf + recvoffset, rc.data(), rd.data(),
                           sendtype.code, nullptr),
           "Allgatherv");
@@ -181,11 +249,16 @@ class Intracomm {
   void Gatherv(const T* sendbuf, int sendoffset, int sendcount, const Datatype& sendtype, T* recvbuf,
                int recvoffset, const std::vector<int>& recvcount, const std::vector<int>& displs,
                const Datatype& recvtype, int root) {
-    same_type<T>(sendtype, recvtype, "Gatherv");
     std::vector<int64_t> rc, rd;
     if (rank_ == root) {
       rc = counts(recvcount);
       rd = counts(displs);
+    }
+    if (strided<T>(sendtype, recvtype, "Gatherv")) {
+      std::vector<int64_t> z(size_, 0), sc(size_, 0);
+      sc[root] = sendcount;
+      return dt_move("Gatherv", sendbuf + sendoffset, sc, z, sendtype, rank_ == root ? recvbuf + recvoffset : nullptr,
+                     rank_ == root ? rc : z, rank_ == root ? rd : z, recvtype);
     }
     check(mpjx_gatherv(c_, sendbuf + sendoffset, sendcount, rank_ == root ? recvbuf + recvoffset : nullptr,
                        rank_ == root ? rc.data() : nullptr, rank_ == root ? rd.data() : nullptr, sendtype.code, root,
@@ -197,11 +270,16 @@ class Intracomm {
   void Scatterv(const T* sendbuf, int sendoffset, const std::vector<int>& sendcount, const std::vector<int>& displs,
                 const Datatype& sendtype, T* recvbuf, int recvoffset, int recvcount, const Datatype& recvtype,
                 int root) {
-    same_type<T>(sendtype, recvtype, "Scatterv");
     std::vector<int64_t> sc, sd;
     if (rank_ == root) {
       sc = counts(sendcount);
       sd = counts(displs);
+    }
+    if (strided<T>(sendtype, recvtype, "Scatterv")) {
+      std::vector<int64_t> z(size_, 0), rc(size_, 0);
+      rc[root] = recvcount;
+      return dt_move("Scatterv", rank_ == root ? sendbuf + sendoffset : nullptr, rank_ == root ? sc : z,
+                     rank_ == root ? sd : z, sendtype, recvbuf + recvoffset, rc, z, recvtype);
     }
     check(mpjx_scatterv(c_, rank_ == root ? sendbuf + sendoffset : nullptr, rank_ == root ? sc.data() : nullptr,
                         rank_ == root ? sd.data() : nullptr, recvbuf + recvoffset, recvcount, sendtype.code, root,
@@ -212,7 +290,12 @@ class Intracomm {
   template <class T>
   void Alltoall(const T* sendbuf, int sendoffset, int sendcount, const Datatype& sendtype, T* recvbuf,
                 int recvoffset, int recvcount, const Datatype& recvtype) {
-    same_type<T>(sendtype, recvtype, "Alltoall");
+    if (strided<T>(sendtype, recvtype, "Alltoall")) {
+      equal_length("Alltoall", sendcount, sendtype, recvcount, recvtype);
+      return dt_move("Alltoall", sendbuf + sendoffset, std::vector<int64_t>(size_, sendcount),
+                     blocks(sendcount, sendtype), sendtype, recvbuf + recvoffset,
+                     std::vector<int64_t>(size_, recvcount), blocks(recvcount, recvtype), recvtype);
+    }
     if (sendcount != recvcount) throw MPIException("Alltoall: sendcount must equal recvcount");
     check(mpjx_alltoall(c_, sendbuf + sendoffset, recvbuf + recvoffset, sendcount, sendtype.code, nullptr),
           "Alltoall");
@@ -222,8 +305,9 @@ class Intracomm {
   void Alltoallv(const T* sendbuf, int sendoffset, const std::vector<int>& sendcount,
                  const std::vector<int>& sdispls, const Datatype& sendtype, T* recvbuf, int recvoffset,
                  const std::vector<int>& recvcount, const std::vector<int>& rdispls, const Datatype& recvtype) {
-    same_type<T>(sendtype, recvtype, "Alltoallv");
     std::vector<int64_t> sc = counts(sendcount), sd = counts(sdispls), rc = counts(recvcount), rd = counts(rdispls);
+    if (strided<T>(sendtype, recvtype, "Alltoallv"))
+      return dt_move("Alltoallv", sendbuf + sendoffset, sc, sd, sendtype, recvbuf + recvoffset, rc, rd, recvtype);
     check(mpjx_alltoallv(c_, sendbuf + sendoffset, sc.data(), sd.data(), recvbuf + recvoffset, rc.data(), rd.data(),
                          sendtype.code, nullptr),
           "Alltoallv");
@@ -288,10 +372,31 @@ class Intracomm {
     if ((int)sizeof(T) != dt.byteSize)
       throw MPIException(std::string("buffer element size does not match MPI.") + dt.name);
   }
+  // True if the call takes the strided path (mpjx_alltoallv_dt): a derived type on either side, or two
+  // different types of one base type. Two equal basic or pair types take the path they always took.
   template <class T>
-  static void same_type(const Datatype& sendtype, const Datatype& recvtype, const char* what) {
-    if (sendtype.code != recvtype.code) throw MPIException(std::string(what) + ": sendtype differs from recvtype");
+  static bool strided(const Datatype& sendtype, const Datatype& recvtype, const char* what) {
+    if (sendtype.Base() != recvtype.Base())
+      throw MPIException(std::string(what) + ": sendtype differs from recvtype in its base type");
     size_ok<T>(sendtype);
+    return sendtype.derived || recvtype.derived || sendtype.code != recvtype.code;
+  }
+  static void equal_length(const char* what, int sendcount, const Datatype& st, int recvcount, const Datatype& rt) {
+    if ((int64_t)sendcount * st.Size() != (int64_t)recvcount * rt.Size())
+      throw MPIException(std::string(what) + ": the send and receive lengths differ");
+  }
+  // Block j of an equal-count call: j * count extents into the buffer, in base elements
+  std::vector<int64_t> blocks(int count, const Datatype& dt) const {
+    std::vector<int64_t> d(size_);
+    for (int j = 0; j < size_; j++) d[j] = (int64_t)j * count * dt.Extent();
+    return d;
+  }
+  void dt_move(const char* what, const void* sendbuf, const std::vector<int64_t>& sc, const std::vector<int64_t>& sd,
+               const Datatype& st, void* recvbuf, const std::vector<int64_t>& rc, const std::vector<int64_t>& rd,
+               const Datatype& rt) {
+    check(mpjx_alltoallv_dt(c_, sendbuf, sc.data(), sd.data(), st.code, recvbuf, rc.data(), rd.data(), rt.code, nullptr),
+          what);
+    sync();
   }
   template <class T>
   static void extent(const std::vector<T>& v, int off, int64_t count, int size = 1) {

@@ -74,6 +74,11 @@ def _declare(L):
         "mpjx_scatterv": ([vp, vp, pi64, pi64, vp, c_i64, c_int, c_int, vp], c_int),
         "mpjx_alltoall": ([vp, vp, vp, c_i64, c_int, vp], c_int),
         "mpjx_alltoallv": ([vp, vp, pi64, pi64, vp, pi64, pi64, c_int, vp], c_int),
+        "mpjx_type_contiguous": ([c_i64, c_int, ctypes.POINTER(c_int)], c_int),
+        "mpjx_type_vector": ([c_i64, c_i64, c_i64, c_int, ctypes.POINTER(c_int)], c_int),
+        "mpjx_type_free": ([c_int], c_int),
+        "mpjx_type_info": ([c_int, ctypes.POINTER(c_int), pi64, pi64], c_int),
+        "mpjx_alltoallv_dt": ([vp, vp, pi64, pi64, c_int, vp, pi64, pi64, c_int, vp], c_int),
         "mpjx_reduce_host": ([vp, vp, vp, c_i64, c_int, c_int, c_int, c_uint], c_int),
         "mpjx_allreduce_host": ([vp, vp, vp, c_i64, c_int, c_int, c_uint], c_int),
         "mpjx_reduce_scatter_host": ([vp, vp, vp, pi64, c_int, c_int, c_uint], c_int),

@@ -1,7 +1,7 @@
 // mpjx_collectives.hip — the reduction collectives of libmpjx (Reduce, Allreduce, Reduce_scatter,
 // Scan), their companions (Bcast, Gather, Scatter), the block moves (Allgather(v), Gatherv, Scatterv,
-// Alltoall(v)), big-endian (mpjbuf) payload handling and the host-resident variants, exported through
-// the C ABI declared in include/mpjx.h.
+// Alltoall(v)) and their form with a derived datatype per side (mpjx_alltoallv_dt), big-endian (mpjbuf)
+// payload handling and the host-resident variants, exported through the C ABI declared in include/mpjx.h.
 //
 // Reference behaviour followed (file:line in /root/reference):
 //   Reduce          src/mpi/PureIntracomm.java:1923-1992 (MST_Reduce), :1994-2057 (FT_Reduce)
@@ -1733,7 +1733,186 @@ int moves_begin(mpjx_comm* c, int type, int* esz) {
   return MPJX_SUCCESS;
 }
 
+// ---- strided moves: mpjx_alltoallv_dt ------------------------------------------------------------------
+// The general block move with a datatype per side (Contiguous / Vector, mpjx_strided_plan.hpp). Per rank, P
+// send layouts and P receive layouts (SideBytes, absolute addresses); a segment moves the packed bytes of
+// a send layout in order into the matching receive layout. A segment whose two layouts are contiguous
+// runs k_moves, every other one k_strided (mpjx_k_strided.hip). The engines are moves_run's:
+//   P = 1                     both types contiguous: the call IS mpjx_alltoallv's (byte ranges, moves_run);
+//                             otherwise one k_strided launch
+//   multicore, one device     share, rank 0 plans and launches the whole world's segments, fence. A
+//                             base-type or packed-length mismatch between a sender and its receiver is
+//                             MPJX_ERR_ARG on every rank before anything moves.
+//   every other world         own block layout to layout; strided sends packed into scratch (one launch),
+//                             the packed bytes through the transport's exchange, strided receives
+//                             unpacked from scratch (one launch). A contiguous side is sent from, or
+//                             received into, its buffer. Matching signatures are the caller's contract.
+
+struct DtPlan {
+  const char* send;
+  char* recv;
+  int base;  // the basic type code both types are made of
+  std::vector<SideBytes> S, R;
+};
+
+int dt_check(mpjx_comm* c, const DtPlan& p) {
+  int64_t st = 0, rt = 0;
+  for (const SideBytes& x : p.S) st += x.total();
+  for (const SideBytes& x : p.R) rt += x.total();
+  if ((st > 0 && !p.send) || (rt > 0 && !p.recv)) return fail(MPJX_ERR_ARG, "NULL buffer with a nonzero count");
+  CHK(check_bufs(c, st > 0 ? p.send : nullptr, rt > 0 ? p.recv : nullptr));
+  int a = 0, b = 0;
+  switch (strided_overlap(p.S, p.R, &a, &b)) {
+    case kRecvOverlap: return fail(MPJX_ERR_ARG, "the receive layouts from ranks %d and %d overlap", a, b);
+    case kSendRecvOverlap:
+      return fail(MPJX_ERR_ARG, "the send layout to rank %d and the receive layout from rank %d overlap "
+                  "(these collectives have no in-place form)", a, b);
+    default: return MPJX_SUCCESS;  // none, or more blocks than the exact check expands: the caller's contract
+  }
+}
+
+// One segment onto the lists of the two kernels
+int dt_add(const SideBytes& s, const SideBytes& d, MoveList* ml, std::vector<StridedSeg>* segs) {
+  if (s.total() <= 0) return MPJX_SUCCESS;
+  if (s.contiguous() && d.contiguous()) {
+    ml->add((void*)(uintptr_t)d.base, (const void*)(uintptr_t)s.base, s.total());
+    return MPJX_SUCCESS;
+  }
+  StridedSeg sg;
+  std::string err;
+  const int rc = plan_strided_seg(s, d, &sg, &err);
+  if (rc != kTypeOk) return fail(rc, "%s", err.c_str());
+  segs->push_back(sg);
+  return MPJX_SUCCESS;
+}
+
+SideBytes packed_at(const char* p, int64_t bytes) {
+  SideBytes x;
+  x.base = (uint64_t)(uintptr_t)p;
+  x.bb = x.sb = x.eb = bytes;
+  x.nb = x.items = 1;
+  return x;
+}
+
+int dt_run(mpjx_comm* c, DtPlan& p, void* stream) {
+  const int P = c->size, me = c->rank;
+  auto* t = dynamic_cast<SmpTransport*>(c->tr.get());
+  const bool world = P > 1 && t && smp_direct(c) && t->single();
+  bool contig = true;
+  for (int j = 0; j < P; j++) contig = contig && p.S[(size_t)j].contiguous() && p.R[(size_t)j].contiguous();
+  if (P == 1 && contig) {  // exactly mpjx_alltoallv on the same bytes
+    MovePlan m{p.send, p.recv, {}, {}};
+    for (int j = 0; j < P; j++) {
+      m.S.push_back(ByteRange{(int64_t)(p.S[(size_t)j].base - (uint64_t)(uintptr_t)p.send), p.S[(size_t)j].total()});
+      m.R.push_back(ByteRange{(int64_t)(p.R[(size_t)j].base - (uint64_t)(uintptr_t)p.recv), p.R[(size_t)j].total()});
+    }
+    return moves_run(c, MV_ALLTOALL, m, p.base, stream);
+  }
+  CHK(dt_check(c, p));
+  Call k;
+  CHK(k.begin(c, stream, p.base));
+  if (p.S[(size_t)me].total() != p.R[(size_t)me].total())
+    return fail(MPJX_ERR_ARG, "rank %d sends itself %lld bytes but receives %lld", me,
+                (long long)p.S[(size_t)me].total(), (long long)p.R[(size_t)me].total());
+  MoveList ml;
+  std::vector<StridedSeg> segs;
+  if (world) {
+    // The layouts stay in this rank's frame: no rank leaves the call before the fence's rendezvous
+    std::vector<std::vector<const void*>> all;
+    CHK(t->share(std::vector<const void*>{&p.S, &p.R, &p.base}, k.s, &all, true));
+    auto S = [&](int i) -> const std::vector<SideBytes>& { return *(const std::vector<SideBytes>*)all[i][0]; };
+    auto R = [&](int i) -> const std::vector<SideBytes>& { return *(const std::vector<SideBytes>*)all[i][1]; };
+    for (int i = 0; i < P; i++)
+      for (int j = 0; j < P; j++) {
+        const long long sl = S(i)[(size_t)j].total(), rl = R(j)[(size_t)i].total();
+        const int sb = *(const int*)all[i][2], rb = *(const int*)all[j][2];
+        if (sl == rl && (sl == 0 || sb == rb)) continue;
+        (void)t->fence(k.s, true);  // every rank has read every table before any rank returns
+        if (sl != rl) return fail(MPJX_ERR_ARG, "rank %d sends %lld bytes to rank %d, which receives %lld", i, sl, j, rl);
+        return fail(MPJX_ERR_ARG, "rank %d sends base type %d to rank %d, which receives base type %d", i, sb, j, rb);
+      }
+    if (me == 0) {
+      for (int j = 0; j < P; j++)    // receiver
+        for (int i = 0; i < P; i++)  // sender
+          DCHK(dt_add(S(i)[(size_t)j], R(j)[(size_t)i], &ml, &segs));
+      HIPCHK(launch_moves(ml, k.s));
+      HIPCHK(launch_strided(segs, k.s));
+    }
+    CHK(t->fence(k.s, true));
+    return k.end();
+  }
+  CHK(dt_add(p.S[(size_t)me], p.R[(size_t)me], &ml, &segs));
+  if (P == 1) {
+    HIPCHK(launch_moves(ml, k.s));
+    HIPCHK(launch_strided(segs, k.s));
+    return k.end();
+  }
+  // scratch slots (16-B aligned) of the strided sends, then of the strided receives
+  std::vector<size_t> so((size_t)P, 0), ro((size_t)P, 0);
+  size_t need = 0;
+  auto slot = [&](const SideBytes& x, size_t* off) {
+    if (x.total() <= 0 || x.contiguous()) return;
+    *off = need;
+    need += ((size_t)x.total() + 15) & ~(size_t)15;
+  };
+  for (int j = 0; j < P; j++)
+    if (j != me) slot(p.S[(size_t)j], &so[(size_t)j]);
+  for (int j = 0; j < P; j++)
+    if (j != me) slot(p.R[(size_t)j], &ro[(size_t)j]);
+  if (need) CHK(k.scratch(need));
+  std::vector<StridedSeg> unpack;
+  std::vector<Xfer> sends, recvs;
+  MoveList none;
+  for (int j = 0; j < P; j++) {
+    if (j == me) continue;
+    const SideBytes& s = p.S[(size_t)j];
+    const SideBytes& r = p.R[(size_t)j];
+    if (s.total() > 0) {
+      char* at = s.contiguous() ? (char*)(uintptr_t)s.base : c->scratch + so[(size_t)j];
+      if (!s.contiguous()) CHK(dt_add(s, packed_at(at, s.total()), &none, &segs));
+      sends.push_back({j, at, (size_t)s.total()});
+    }
+    if (r.total() > 0) {
+      char* at = r.contiguous() ? (char*)(uintptr_t)r.base : c->scratch + ro[(size_t)j];
+      if (!r.contiguous()) CHK(dt_add(packed_at(at, r.total()), r, &none, &unpack));
+      recvs.push_back({j, at, (size_t)r.total()});
+    }
+  }
+  HIPCHK(launch_moves(ml, k.s));
+  HIPCHK(launch_strided(segs, k.s));  // the own block and every peer's pack: one launch per table
+  CHK(c->tr->exchange(sends, recvs, k.s));
+  HIPCHK(launch_strided(unpack, k.s));
+  return k.end();
+}
+
+int dt_table(const TypeForm& f, const void* buf, const int64_t* counts, const int64_t* displs, int n,
+             std::vector<SideBytes>* out, const char* what) {
+  if (!counts || !displs) return fail(MPJX_ERR_ARG, "%s or their displacements are NULL", what);
+  out->assign((size_t)n, SideBytes{});
+  std::string err;
+  for (int j = 0; j < n; j++)
+    if (!plan_side(f, (uint64_t)(uintptr_t)buf, counts[j], displs[j], &(*out)[(size_t)j], &err, what))
+      return fail(MPJX_ERR_ARG, "%s at index %d", err.c_str(), j);
+  return MPJX_SUCCESS;
+}
+
 }  // namespace
+
+static int alltoallv_dt_entry(mpjx_comm_t c, const void* sendbuf, const int64_t* sendcounts, const int64_t* sdispls,
+                              int sendtype, void* recvbuf, const int64_t* recvcounts, const int64_t* rdispls,
+                              int recvtype, void* stream) {
+  if (!c) return fail(MPJX_ERR_ARG, "comm is NULL");
+  TypeForm st, rt;
+  if (!type_form(sendtype, &st)) return fail(MPJX_ERR_ARG, "unknown or freed datatype code %d", sendtype);
+  if (!type_form(recvtype, &rt)) return fail(MPJX_ERR_ARG, "unknown or freed datatype code %d", recvtype);
+  if (st.base != rt.base)
+    return fail(MPJX_ERR_ARG, "sendtype %d (base type %d) and recvtype %d (base type %d) differ in their base type",
+                sendtype, st.base, recvtype, rt.base);
+  DtPlan p{(const char*)sendbuf, (char*)recvbuf, st.base, {}, {}};
+  CHK(dt_table(st, sendbuf, sendcounts, sdispls, c->size, &p.S, "sendcounts"));
+  CHK(dt_table(rt, recvbuf, recvcounts, rdispls, c->size, &p.R, "recvcounts"));
+  return dt_run(c, p, stream);
+}
 
 static int allgather_entry(mpjx_comm_t c, const void* sendbuf, void* recvbuf, int64_t count, int type, void* stream) {
   int esz;
@@ -1854,6 +2033,13 @@ extern "C" int mpjx_alltoallv(mpjx_comm_t c, const void* sendbuf, const int64_t*
                               void* recvbuf, const int64_t* recvcounts, const int64_t* rdispls, int type,
                               void* stream) {
   return ended(c, alltoallv_entry(c, sendbuf, sendcounts, sdispls, recvbuf, recvcounts, rdispls, type, stream));
+}
+
+extern "C" int mpjx_alltoallv_dt(mpjx_comm_t c, const void* sendbuf, const int64_t* sendcounts,
+                                 const int64_t* sdispls, int sendtype, void* recvbuf, const int64_t* recvcounts,
+                                 const int64_t* rdispls, int recvtype, void* stream) {
+  return ended(c, alltoallv_dt_entry(c, sendbuf, sendcounts, sdispls, sendtype, recvbuf, recvcounts, rdispls, recvtype,
+                                     stream));
 }
 
 extern "C" int mpjx_allreduce(mpjx_comm_t c, const void* sendbuf, void* recvbuf, int64_t count, int type, int op,

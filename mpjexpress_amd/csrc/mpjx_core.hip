@@ -63,6 +63,45 @@ extern "C" int mpjx_type_size(int type) {
   return 0;
 }
 
+// ---- derived datatypes (mpjx_strided_plan.hpp: the normal form and the registry) ------------------------
+static int type_new(int rc, const TypeForm& f, const std::string& err, const char* what, int* newtype) {
+  if (rc != kTypeOk) return fail(rc, "%s: %s", what, err.c_str());
+  *newtype = TypeRegistry::get().add(f);
+  return MPJX_SUCCESS;
+}
+
+extern "C" int mpjx_type_contiguous(int64_t count, int oldtype, int* newtype) {
+  if (!newtype) return fail(MPJX_ERR_ARG, "NULL argument");
+  TypeForm old, f;
+  if (!type_form(oldtype, &old)) return fail(MPJX_ERR_ARG, "unknown or freed datatype code %d", oldtype);
+  std::string err;
+  const int rc = contiguous_of(count, old, &f, &err);
+  return type_new(rc, f, err, "Contiguous", newtype);
+}
+
+extern "C" int mpjx_type_vector(int64_t count, int64_t blocklength, int64_t stride, int oldtype, int* newtype) {
+  if (!newtype) return fail(MPJX_ERR_ARG, "NULL argument");
+  TypeForm old, f;
+  if (!type_form(oldtype, &old)) return fail(MPJX_ERR_ARG, "unknown or freed datatype code %d", oldtype);
+  std::string err;
+  const int rc = vector_form(count, blocklength, stride, old, &f, &err);
+  return type_new(rc, f, err, "Vector", newtype);
+}
+
+extern "C" int mpjx_type_free(int type) {
+  if (!TypeRegistry::get().release(type)) return fail(MPJX_ERR_ARG, "unknown or freed derived datatype code %d", type);
+  return MPJX_SUCCESS;
+}
+
+extern "C" int mpjx_type_info(int type, int* base, int64_t* size, int64_t* extent) {
+  TypeForm f;
+  if (!type_form(type, &f)) return fail(MPJX_ERR_ARG, "unknown or freed datatype code %d", type);
+  if (base) *base = f.base;
+  if (size) *size = f.size();
+  if (extent) *extent = f.extent();
+  return MPJX_SUCCESS;
+}
+
 extern "C" int mpjx_op_check(int op, int type) {
   if (mpjx_type_size(type) == 0) return fail(MPJX_ERR_ARG, "unknown datatype code %d", type);
   if (op == MPJX_MAXLOC || op == MPJX_MINLOC) {  // Maxloc.java / Minloc.java: pair types only

@@ -50,9 +50,53 @@ class Datatype:
         self.code = base_type if size == 1 else (0x100 | base_type)
         self.baseSize = self.np_dtype.itemsize
         self.byteSize = self.baseSize * size
+        self.extent = size  # base elements from one item to the next
+        self.derived = False
+
+    @classmethod
+    def _derived(cls, code, old, name):
+        """The Datatype of a derived code the library handed out (mpjx_type_contiguous / mpjx_type_vector)."""
+        base, size, extent = ctypes.c_int(), ctypes.c_int64(), ctypes.c_int64()
+        _wrap("mpjx_type_info", code, ctypes.byref(base), ctypes.byref(size), ctypes.byref(extent))
+        dt = cls(base.value, name, old.np_dtype, old.torch_dtype_name)
+        dt.size, dt.extent, dt.code, dt.derived = size.value, extent.value, code, True
+        dt.byteSize = dt.baseSize * dt.size
+        return dt
+
+    @classmethod
+    def Contiguous(cls, count, oldtype):
+        """Datatype.Contiguous (src/mpi/Contiguous.java): `count` items of oldtype in a row."""
+        code = ctypes.c_int()
+        _wrap("mpjx_type_contiguous", count, oldtype.code, ctypes.byref(code))
+        return cls._derived(code.value, oldtype, f"Contiguous({count}, {oldtype.name})")
+
+    @classmethod
+    def Vector(cls, count, blocklength, stride, oldtype):
+        """Datatype.Vector (src/mpi/Vector.java): `count` blocks of `blocklength` items of oldtype, `stride`
+        items of oldtype apart. oldtype is basic, a pair type or contiguous; stride >= blocklength."""
+        code = ctypes.c_int()
+        _wrap("mpjx_type_vector", count, blocklength, stride, oldtype.code, ctypes.byref(code))
+        return cls._derived(code.value, oldtype, f"Vector({count}, {blocklength}, {stride}, {oldtype.name})")
+
+    def Commit(self):
+        pass
+
+    def Free(self):
+        """Release a derived type's code; the library rejects it in every later call."""
+        if self.derived:
+            _wrap("mpjx_type_free", self.code)
 
     def Size(self):
         return self.size
+
+    def Extent(self):
+        return self.extent
+
+    def Lb(self):
+        return 0
+
+    def Ub(self):
+        return self.extent
 
     def __repr__(self):
         return f"MPI.{self.name}"
@@ -362,12 +406,46 @@ class Intracomm:
     # in elements. One k_moves launch at P = 1 and in one-device multicore worlds, the transport's
     # exchanges elsewhere (include/mpjx.h).
     def _moves(self, name, sendbuf, sendtype, recvbuf, recvtype):
-        if sendtype is not recvtype and sendtype.code != recvtype.code:
-            raise MPIException(f"{name}: sendtype {sendtype} differs from recvtype {recvtype}")
+        """True if the call takes the strided path (mpjx_alltoallv_dt): a derived type on either side, or two
+        different types of one base type. Two equal basic or pair types take the path they always took."""
+        if sendtype.baseType != recvtype.baseType:
+            raise MPIException(f"{name}: sendtype {sendtype} differs from recvtype {recvtype} in its base type")
         for b in (sendbuf, recvbuf):
             if b is not None and not _is_torch(b):
                 raise MPIException(f"{name} is provided for device-resident buffers")
         self._sync_in(*(b for b in (sendbuf, recvbuf) if b is not None))
+        return sendtype.derived or recvtype.derived or sendtype.code != recvtype.code
+
+    def _dt_side(self, name, buf, off, dt, counts, displs):
+        """(address, counts, displacements) of one side of mpjx_alltoallv_dt: counts in items of dt,
+        displacements in base elements; the buffer must hold every layout's true span."""
+        P = self._size
+        c, d = [int(x) for x in counts][:P], [int(x) for x in displs][:P]
+        if len(c) < P or len(d) < P:
+            raise MPIException(f"{name}: counts or displacements shorter than the communicator")
+        arr = ctypes.c_int64 * P
+        span = max([dj + cj * dt.extent for cj, dj in zip(c, d) if cj > 0 and dt.size > 0] or [0])
+        if span == 0 and buf is None:
+            return None, arr(*c), arr(*d)
+        if not buf.is_cuda:
+            raise MPIException("torch tensor buffers must be on a GPU device")
+        if not buf.is_contiguous():
+            raise MPIException("buffer must be contiguous")
+        if buf.element_size() != dt.baseSize:
+            raise MPIException(f"buffer element size {buf.element_size()} does not match {dt}")
+        if off < 0 or min(d) < 0 or off + span > buf.numel():
+            raise MPIException(f"{name}: offset {off} + layout span {span} exceeds buffer length {buf.numel()}")
+        return buf.data_ptr() + off * dt.baseSize, arr(*c), arr(*d)
+
+    def _dt(self, name, sendbuf, soff, sc, sd, stype, recvbuf, roff, rc, rd, rtype):
+        sp, sca, sda = self._dt_side(name, sendbuf, soff, stype, sc, sd)
+        rp, rca, rda = self._dt_side(name, recvbuf, roff, rtype, rc, rd)
+        _wrap("mpjx_alltoallv_dt", self._h, sp, sca, sda, stype.code, rp, rca, rda, rtype.code, None)
+        self._sync_out()
+
+    def _equal(self, name, sendcount, sendtype, recvcount, recvtype):
+        if sendcount * sendtype.size != recvcount * recvtype.size:
+            raise MPIException(f"{name}: {sendcount} x {sendtype} and {recvcount} x {recvtype} differ in length")
 
     def _table(self, name, counts, displs):
         """(counts, displs as int64 arrays, elements spanned) of one rank's count/displacement lists."""
@@ -379,7 +457,11 @@ class Intracomm:
         return arr(*c), arr(*d), span
 
     def Allgather(self, sendbuf, sendoffset, sendcount, sendtype, recvbuf, recvoffset, recvcount, recvtype):
-        self._moves("Allgather", sendbuf, sendtype, recvbuf, recvtype)
+        if self._moves("Allgather", sendbuf, sendtype, recvbuf, recvtype):
+            self._equal("Allgather", sendcount, sendtype, recvcount, recvtype)
+            P, z = self._size, [0] * self._size
+            return self._dt("Allgather", sendbuf, sendoffset, [sendcount] * P, z, sendtype, recvbuf, recvoffset,
+                            [recvcount] * P, [j * recvcount * recvtype.extent for j in range(P)], recvtype)
         if sendcount != recvcount:
             raise MPIException("Allgather: sendcount must equal recvcount")
         sp = _dev_ptr(sendbuf, sendoffset, sendtype, sendcount)
@@ -389,7 +471,10 @@ class Intracomm:
 
     def Allgatherv(self, sendbuf, sendoffset, sendcount, sendtype, recvbuf, recvoffset, recvcount, displs,
                    recvtype):
-        self._moves("Allgatherv", sendbuf, sendtype, recvbuf, recvtype)
+        if self._moves("Allgatherv", sendbuf, sendtype, recvbuf, recvtype):
+            P = self._size
+            return self._dt("Allgatherv", sendbuf, sendoffset, [sendcount] * P, [0] * P, sendtype, recvbuf,
+                            recvoffset, recvcount, displs, recvtype)
         rc, rd, span = self._table("Allgatherv", recvcount, displs)
         sp = _dev_ptr(sendbuf, sendoffset, sendtype, sendcount)
         rp = _dev_ptr(recvbuf, recvoffset, recvtype, span)
@@ -400,7 +485,11 @@ class Intracomm:
                 recvtype, root):
         """recvbuf, recvcount and displs are significant at the root only."""
         is_root = self._rank == root
-        self._moves("Gatherv", sendbuf, sendtype, recvbuf if is_root else None, recvtype)
+        if self._moves("Gatherv", sendbuf, sendtype, recvbuf if is_root else None, recvtype):
+            z = [0] * self._size
+            return self._dt("Gatherv", sendbuf, sendoffset, [sendcount if j == root else 0 for j in range(self._size)],
+                            z, sendtype, recvbuf if is_root else None, recvoffset, recvcount if is_root else z,
+                            displs if is_root else z, recvtype)
         rc = rd = rp = None
         if is_root:
             rc, rd, span = self._table("Gatherv", recvcount, displs)
@@ -413,7 +502,11 @@ class Intracomm:
                  recvtype, root):
         """sendbuf, sendcount and displs are significant at the root only."""
         is_root = self._rank == root
-        self._moves("Scatterv", sendbuf if is_root else None, sendtype, recvbuf, recvtype)
+        if self._moves("Scatterv", sendbuf if is_root else None, sendtype, recvbuf, recvtype):
+            z = [0] * self._size
+            return self._dt("Scatterv", sendbuf if is_root else None, sendoffset, sendcount if is_root else z,
+                            displs if is_root else z, sendtype, recvbuf, recvoffset,
+                            [recvcount if j == root else 0 for j in range(self._size)], z, recvtype)
         sc = sd = sp = None
         if is_root:
             sc, sd, span = self._table("Scatterv", sendcount, displs)
@@ -423,7 +516,12 @@ class Intracomm:
         self._sync_out()
 
     def Alltoall(self, sendbuf, sendoffset, sendcount, sendtype, recvbuf, recvoffset, recvcount, recvtype):
-        self._moves("Alltoall", sendbuf, sendtype, recvbuf, recvtype)
+        if self._moves("Alltoall", sendbuf, sendtype, recvbuf, recvtype):
+            self._equal("Alltoall", sendcount, sendtype, recvcount, recvtype)
+            P = self._size
+            return self._dt("Alltoall", sendbuf, sendoffset, [sendcount] * P,
+                            [j * sendcount * sendtype.extent for j in range(P)], sendtype, recvbuf, recvoffset,
+                            [recvcount] * P, [j * recvcount * recvtype.extent for j in range(P)], recvtype)
         if sendcount != recvcount:
             raise MPIException("Alltoall: sendcount must equal recvcount")
         sp = _dev_ptr(sendbuf, sendoffset, sendtype, sendcount * self._size)
@@ -433,7 +531,9 @@ class Intracomm:
 
     def Alltoallv(self, sendbuf, sendoffset, sendcount, sdispls, sendtype, recvbuf, recvoffset, recvcount,
                   rdispls, recvtype):
-        self._moves("Alltoallv", sendbuf, sendtype, recvbuf, recvtype)
+        if self._moves("Alltoallv", sendbuf, sendtype, recvbuf, recvtype):
+            return self._dt("Alltoallv", sendbuf, sendoffset, sendcount, sdispls, sendtype, recvbuf, recvoffset,
+                            recvcount, rdispls, recvtype)
         sc, sd, sspan = self._table("Alltoallv", sendcount, sdispls)
         rc, rd, rspan = self._table("Alltoallv", recvcount, rdispls)
         sp = _dev_ptr(sendbuf, sendoffset, sendtype, sspan)
@@ -445,6 +545,14 @@ class Intracomm:
         if not _is_torch(buf):
             raise MPIException("Bcast is provided for device-resident buffers")
         self._sync_in(buf)
+        if datatype.derived:
+            # the root sends to every other rank; its own entry stays empty (the same bytes on both sides)
+            P, z, me = self._size, [0] * self._size, self._rank
+            if me == root:
+                return self._dt("Bcast", buf, offset, [0 if j == root else count for j in range(P)], z, datatype,
+                                None, 0, z, z, datatype)
+            return self._dt("Bcast", None, 0, z, z, datatype, buf, offset,
+                            [count if j == root else 0 for j in range(P)], z, datatype)
         p = _dev_ptr(buf, offset, datatype, count)
         _wrap("mpjx_bcast", self._h, p, count, datatype.code, root, None)
         self._sync_out()
@@ -457,6 +565,15 @@ def _gs(fn, comm, sendbuf, sendoffset, sendcount, recvbuf, recvoffset, recvcount
         raise MPIException("sendcount must equal recvcount")
     comm._sync_in(*(b for b in (sendbuf, recvbuf) if b is not None))
     is_root = comm.Rank() == root
+    if datatype.derived:  # block j of the root's side starts at j * count extents
+        P, z = comm.Size(), [0] * comm.Size()
+        blocks = [j * sendcount * datatype.extent for j in range(P)]
+        one = [sendcount if j == root else 0 for j in range(P)]
+        if send_all:
+            return comm._dt("Scatter", sendbuf if is_root else None, sendoffset, [sendcount] * P if is_root else z,
+                            blocks if is_root else z, datatype, recvbuf, recvoffset, one, z, datatype)
+        return comm._dt("Gather", sendbuf, sendoffset, one, z, datatype, recvbuf if is_root else None, recvoffset,
+                        [recvcount] * P if is_root else z, blocks if is_root else z, datatype)
     n_send = sendcount * (comm.Size() if (send_all and is_root) else 1)
     n_recv = recvcount * (comm.Size() if (not send_all and is_root) else 1)
     sp = _dev_ptr(sendbuf, sendoffset, datatype, n_send) if (is_root or not send_all) else None
