@@ -344,7 +344,7 @@ int mpjx_alltoallv(mpjx_comm_t comm, const void *sendbuf, const int64_t *sendcou
  *   MPJX_ERR_ARG: a negative count or blocklength, an unknown or freed oldtype, sizes beyond 2^62 bytes.
  *   MPJX_ERR_UNSUPPORTED (the message names what was passed): a stride smaller than the block length
  *   (negative, zero or overlapping), a strided oldtype (Vector of Vector, Contiguous of Vector).
- * Hvector, Indexed, Hindexed, Struct and the LB/UB markers are not provided.
+ * Struct and the LB/UB markers are not provided (their sticky bounds are a separate piece of semantics).
  * Derived codes are handles >= 0x10000 from a process-wide, thread-safe registry, local to the rank as MPI
  * types are (only the signatures must match between ranks). A freed code is never reissued; a freed or
  * unknown code is MPJX_ERR_ARG in every later call. mpjx_type_size() returns 0 for a derived code, so every
@@ -354,6 +354,39 @@ int mpjx_type_contiguous(int64_t count, int oldtype, int *newtype);
 int mpjx_type_vector(int64_t count, int64_t blocklength, int64_t stride, int oldtype, int *newtype);
 int mpjx_type_free(int type);
 int mpjx_type_info(int type, int *base, int64_t *size, int64_t *extent);
+/* ---- irregular datatypes (src/mpi/Hvector.java, src/mpi/Indexed.java, src/mpi/Hindexed.java) ------------
+ * A list of blocks (offset, length) in elements of the basic type from the item's origin, kept in PACK order:
+ * the order of the constructor's arrays, not address order.
+ *   Indexed(bl[], disp[], old)   block i is bl[i] items of old, old.extent apart, starting disp[i]*old.extent
+ *                                elements from the origin
+ *   Hindexed                     the same, but block i starts at disp[i] elements: mpiJava's "H" units are
+ *                                buffer indices, not bytes
+ *   Hvector(count, bl, stride, old)   block j starts j*stride elements from the origin
+ * size = sum bl*old.size; lb = the minimum over non-empty blocks of start + old.lb; ub = the maximum of
+ * start + (bl-1)*old.extent + old.ub; extent = ub - lb; an empty type has all four 0. Zero-length blocks take
+ * no part in the bounds. Item k of a message starts k*extent after item 0's origin and block offsets are added
+ * to that origin: lb is NOT subtracted, so Indexed([2],[3],INT) has lb 3 and extent 2 and its item k is elements
+ * 3+2k, 4+2k past the buffer position.
+ * oldtype is any live type: basic, pair, Contiguous, Vector or one of these. A non-contiguous oldtype is
+ * flattened into the list; consecutive blocks that abut in pack order and in address order are merged. A list
+ * that is regular (equal lengths at a constant positive stride of at least the length, in order, first offset
+ * 0) IS the Vector of that shape and takes its path. mpjx_type_vector and mpjx_type_contiguous still reject
+ * every non-contiguous oldtype: Hvector(c, b, s*old.extent, old) is the supported spelling of a Vector of a
+ * Vector.
+ * A type whose own blocks share a byte is legal to send; as a receive type it is MPJX_ERR_ARG.
+ *   MPJX_ERR_ARG: a negative block length or count, n < 0, NULL arrays with n > 0, an unknown or freed
+ *   oldtype, sizes beyond 2^62 bytes.
+ *   MPJX_ERR_UNSUPPORTED (the message names what was passed): a negative displacement (lb < 0), an Hvector
+ *   stride < 1 with count > 1, more than 1,048,576 blocks after merging (a type's device table is 16 B per
+ *   block).
+ * mpjx_type_layout: lb and ub in elements of the basic type (0 and the extent for every regular type), the
+ * merged block count, and regular = 1 if the type takes the block-move or strided kernel, 0 if the indexed
+ * one. mpjx_type_info, mpjx_type_free and mpjx_alltoallv_dt take the new codes like the others; a call
+ * enqueued before mpjx_type_free completes with the layout it was given. */
+int mpjx_type_hvector(int64_t count, int64_t blocklength, int64_t stride, int oldtype, int *newtype);
+int mpjx_type_indexed(int n, const int64_t *blocklengths, const int64_t *displacements, int oldtype, int *newtype);
+int mpjx_type_hindexed(int n, const int64_t *blocklengths, const int64_t *displacements, int oldtype, int *newtype);
+int mpjx_type_layout(int type, int64_t *lb, int64_t *ub, int64_t *nblocks, int *regular);
 /* The general block move: sendcounts[j] items of sendtype, the first at sendbuf + sdispls[j], go to rank j;
  * recvcounts[i] items of recvtype from rank i land from recvbuf + rdispls[i]. Every block move and every
  * rooted call is a special case, with zero counts where a rank has nothing to send or receive.
@@ -370,9 +403,11 @@ int mpjx_type_info(int type, int *base, int64_t *size, int64_t *extent);
  *   call's tables hold at most 65,536 blocks in total; beyond that it is skipped and disjoint layouts are
  *   the caller's contract, as in MPI.
  *   MPJX_ERR_UNSUPPORTED: one message of 2^32 or more granules (the largest power of two <= 16 B that divides
- *   both layouts' block bytes, strides, extents and addresses).
+ *   both layouts' block bytes, strides, extents and addresses; for an irregular type, every block offset and length).
  * No flags and no faithful mode. Enqueued on `stream`, ordered and failure-marked like the other collectives.
- * A segment whose two layouts are contiguous runs the block-move kernel, every other one the strided kernel.
+ * A segment whose two layouts are contiguous runs the block-move kernel, one whose two layouts are regular the
+ * strided kernel, every other one the indexed kernel (a binary search of the type's block table per granule; the
+ * table is uploaded once per communicator and type, on the stream of the first call that uses it).
  * One rank, and multicore ranks sharing one device (MPJX_SMP_COPY unset): one launch per kernel for the whole
  * world; a base-type or packed-length mismatch between a sender and its receiver is MPJX_ERR_ARG on every
  * rank before anything moves. In every other world the rank's own block moves from layout to layout, strided

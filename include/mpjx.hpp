@@ -41,7 +41,7 @@ inline void check(int status, const char* what) {
 // A basic type, or a (value, index) pair type SHORT2..DOUBLE2 = Contiguous(2, base)
 // (src/mpi/MPI.java:110-114): `code` crosses the C ABI; buffers are arrays of the base type,
 // offsets are base-element indices, counts are datatype elements (pairs).
-// A derived type (Contiguous, Vector) owns a code of the library's registry until Free(), as in mpiJava;
+// A derived type (Contiguous, Vector, Hvector, Indexed, Hindexed) owns a code of the library's registry until Free(), as in mpiJava;
 // copies share it.
 struct Datatype {
   int code;
@@ -51,10 +51,11 @@ struct Datatype {
   int extent = 0;    // base elements from one item to the next (0: size)
   int base = 0;      // the basic type's code (0: code & 0xff)
   bool derived = false;
+  int lb = 0;        // lowest base element of an item from its origin (mpjx_type_layout)
   int Size() const { return size; }
   int Extent() const { return extent ? extent : size; }
-  int Lb() const { return 0; }
-  int Ub() const { return Extent(); }
+  int Lb() const { return lb; }
+  int Ub() const { return lb + Extent(); }
   int Base() const { return base ? base : (code & 0xff); }
   void Commit() const {}
   void Free() {
@@ -72,16 +73,42 @@ struct Datatype {
     check(mpjx_type_vector(count, blocklength, stride, oldtype.code, &code), "Datatype.Vector");
     return made(code, oldtype, "Vector");
   }
+  // block j starts j * stride BASE elements from the origin; oldtype is any type (src/mpi/Hvector.java)
+  static Datatype Hvector(int count, int blocklength, int stride, const Datatype& oldtype) {
+    int code = 0;
+    check(mpjx_type_hvector(count, blocklength, stride, oldtype.code, &code), "Datatype.Hvector");
+    return made(code, oldtype, "Hvector");
+  }
+  // block i: blocklengths[i] items of oldtype from displacements[i] extents of oldtype (src/mpi/Indexed.java)
+  static Datatype Indexed(const std::vector<int>& blocklengths, const std::vector<int>& displacements,
+                          const Datatype& oldtype) {
+    return indexed(mpjx_type_indexed, "Datatype.Indexed", blocklengths, displacements, oldtype);
+  }
+  // as Indexed, with displacements in BASE elements (src/mpi/Hindexed.java)
+  static Datatype Hindexed(const std::vector<int>& blocklengths, const std::vector<int>& displacements,
+                           const Datatype& oldtype) {
+    return indexed(mpjx_type_hindexed, "Datatype.Hindexed", blocklengths, displacements, oldtype);
+  }
+  static Datatype indexed(int (*fn)(int, const int64_t*, const int64_t*, int, int*), const char* name,
+                          const std::vector<int>& bl, const std::vector<int>& ds, const Datatype& oldtype) {
+    if (bl.size() != ds.size()) throw MPIException(std::string(name) + ": the two arrays differ in length");
+    const std::vector<int64_t> b(bl.begin(), bl.end()), d(ds.begin(), ds.end());
+    int code = 0;
+    check(fn((int)b.size(), b.data(), d.data(), oldtype.code, &code), name);
+    return made(code, oldtype, name);
+  }
   // the Datatype of a code the library handed out
   static Datatype made(int code, const Datatype& oldtype, const char* name) {
     int base = 0;
     int64_t size = 0, extent = 0;
+    int64_t lb = 0;
     check(mpjx_type_info(code, &base, &size, &extent), "mpjx_type_info");
-    if (size > INT32_MAX || extent > INT32_MAX) {
+    check(mpjx_type_layout(code, &lb, nullptr, nullptr, nullptr), "mpjx_type_layout");
+    if (size > INT32_MAX || lb + extent > INT32_MAX) {
       (void)mpjx_type_free(code);
       throw MPIException(std::string(name) + ": the type exceeds this mirror's int sizes");
     }
-    return Datatype{code, oldtype.byteSize, name, (int)size, (int)extent, base, true};
+    return Datatype{code, oldtype.byteSize, name, (int)size, (int)extent, base, true, (int)lb};
   }
 };
 

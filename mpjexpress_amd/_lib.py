@@ -76,6 +76,10 @@ def _declare(L):
         "mpjx_alltoallv": ([vp, vp, pi64, pi64, vp, pi64, pi64, c_int, vp], c_int),
         "mpjx_type_contiguous": ([c_i64, c_int, ctypes.POINTER(c_int)], c_int),
         "mpjx_type_vector": ([c_i64, c_i64, c_i64, c_int, ctypes.POINTER(c_int)], c_int),
+        "mpjx_type_hvector": ([c_i64, c_i64, c_i64, c_int, ctypes.POINTER(c_int)], c_int),
+        "mpjx_type_indexed": ([c_int, pi64, pi64, c_int, ctypes.POINTER(c_int)], c_int),
+        "mpjx_type_hindexed": ([c_int, pi64, pi64, c_int, ctypes.POINTER(c_int)], c_int),
+        "mpjx_type_layout": ([c_int, pi64, pi64, pi64, ctypes.POINTER(c_int)], c_int),
         "mpjx_type_free": ([c_int], c_int),
         "mpjx_type_info": ([c_int, ctypes.POINTER(c_int), pi64, pi64], c_int),
         "mpjx_alltoallv_dt": ([vp, vp, pi64, pi64, c_int, vp, pi64, pi64, c_int, vp], c_int),

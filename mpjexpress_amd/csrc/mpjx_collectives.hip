@@ -1734,12 +1734,15 @@ int moves_begin(mpjx_comm* c, int type, int* esz) {
 }
 
 // ---- strided moves: mpjx_alltoallv_dt ------------------------------------------------------------------
-// The general block move with a datatype per side (Contiguous / Vector, mpjx_strided_plan.hpp). Per rank, P
-// send layouts and P receive layouts (SideBytes, absolute addresses); a segment moves the packed bytes of
-// a send layout in order into the matching receive layout. A segment whose two layouts are contiguous
-// runs k_moves, every other one k_strided (mpjx_k_strided.hip). The engines are moves_run's:
+// The general block move with a datatype per side (Contiguous / Vector, mpjx_strided_plan.hpp; Hvector /
+// Indexed / Hindexed, mpjx_indexed_plan.hpp). Per rank, P send layouts and P receive layouts (SideBytes,
+// absolute addresses); a segment moves the packed bytes of a send layout in order into the matching receive
+// layout. A segment whose two layouts are contiguous runs k_moves, one whose two layouts are regular
+// k_strided (mpjx_k_strided.hip), every other one k_indexed (mpjx_k_indexed.hip), whose irregular sides read
+// their type's device table from the launching communicator's cache (idx_table). "Strided" below means
+// "not contiguous". The engines are moves_run's:
 //   P = 1                     both types contiguous: the call IS mpjx_alltoallv's (byte ranges, moves_run);
-//                             otherwise one k_strided launch
+//                             otherwise one k_strided or k_indexed launch
 //   multicore, one device     share, rank 0 plans and launches the whole world's segments, fence. A
 //                             base-type or packed-length mismatch between a sender and its receiver is
 //                             MPJX_ERR_ARG on every rank before anything moves.
@@ -1771,18 +1774,59 @@ int dt_check(mpjx_comm* c, const DtPlan& p) {
   }
 }
 
-// One segment onto the lists of the two kernels
-int dt_add(const SideBytes& s, const SideBytes& d, MoveList* ml, std::vector<StridedSeg>* segs) {
+// The segments of one step of a call, by the kernel that runs them: one launch per kernel per table
+struct DtMoves {
+  MoveList ml;
+  std::vector<StridedSeg> st;
+  std::vector<IndexedSeg> ix;
+  hipError_t launch(hipStream_t s) {
+    hipError_t e = launch_moves(ml, s);
+    if (e == hipSuccess) e = launch_strided(st, s);
+    if (e == hipSuccess) e = launch_indexed(ix, s);
+    return e;
+  }
+};
+
+// The device table of an irregular layout, from c's cache: uploaded on `s` at first use. The cache entry
+// keeps the host list alive, so the copy's source outlives it.
+int idx_table(mpjx_comm* c, const SideBytes& x, hipStream_t s, const IdxEnt** out) {
+  *out = nullptr;
+  if (!x.irr) return MPJX_SUCCESS;
+  auto it = c->idx_tables.find(x.code);
+  if (it == c->idx_tables.end()) {
+    void* dev = nullptr;
+    const size_t bytes = x.irr->tab.size() * sizeof(IdxEnt);
+    HIPCHK(hipMalloc(&dev, bytes));
+    c->retired.push_back(dev);  // freed with the communicator
+    HIPCHK(hipMemcpyAsync(dev, x.irr->tab.data(), bytes, hipMemcpyHostToDevice, s));
+    it = c->idx_tables.emplace(x.code, mpjx_comm::IdxTable{(const IdxEnt*)dev, x.irr}).first;
+  }
+  *out = it->second.dev;
+  return MPJX_SUCCESS;
+}
+
+// One segment onto the lists of the three kernels
+int dt_add(mpjx_comm* c, hipStream_t st, const SideBytes& s, const SideBytes& d, DtMoves* m) {
   if (s.total() <= 0) return MPJX_SUCCESS;
   if (s.contiguous() && d.contiguous()) {
-    ml->add((void*)(uintptr_t)d.base, (const void*)(uintptr_t)s.base, s.total());
+    m->ml.add((void*)(uintptr_t)d.base, (const void*)(uintptr_t)s.base, s.total());
     return MPJX_SUCCESS;
   }
-  StridedSeg sg;
   std::string err;
-  const int rc = plan_strided_seg(s, d, &sg, &err);
+  if (s.regular() && d.regular()) {
+    StridedSeg sg;
+    const int rc = plan_strided_seg(s, d, &sg, &err);
+    if (rc != kTypeOk) return fail(rc, "%s", err.c_str());
+    m->st.push_back(sg);
+    return MPJX_SUCCESS;
+  }
+  const IdxEnt *stab, *dtab;
+  CHK(idx_table(c, s, st, &stab));
+  CHK(idx_table(c, d, st, &dtab));
+  IndexedSeg sg;
+  const int rc = plan_indexed_seg(s, stab, d, dtab, &sg, &err);
   if (rc != kTypeOk) return fail(rc, "%s", err.c_str());
-  segs->push_back(sg);
+  m->ix.push_back(sg);
   return MPJX_SUCCESS;
 }
 
@@ -1814,8 +1858,7 @@ int dt_run(mpjx_comm* c, DtPlan& p, void* stream) {
   if (p.S[(size_t)me].total() != p.R[(size_t)me].total())
     return fail(MPJX_ERR_ARG, "rank %d sends itself %lld bytes but receives %lld", me,
                 (long long)p.S[(size_t)me].total(), (long long)p.R[(size_t)me].total());
-  MoveList ml;
-  std::vector<StridedSeg> segs;
+  DtMoves mv;
   if (world) {
     // The layouts stay in this rank's frame: no rank leaves the call before the fence's rendezvous
     std::vector<std::vector<const void*>> all;
@@ -1834,17 +1877,15 @@ int dt_run(mpjx_comm* c, DtPlan& p, void* stream) {
     if (me == 0) {
       for (int j = 0; j < P; j++)    // receiver
         for (int i = 0; i < P; i++)  // sender
-          DCHK(dt_add(S(i)[(size_t)j], R(j)[(size_t)i], &ml, &segs));
-      HIPCHK(launch_moves(ml, k.s));
-      HIPCHK(launch_strided(segs, k.s));
+          DCHK(dt_add(c, k.s, S(i)[(size_t)j], R(j)[(size_t)i], &mv));
+      HIPCHK(mv.launch(k.s));
     }
     CHK(t->fence(k.s, true));
     return k.end();
   }
-  CHK(dt_add(p.S[(size_t)me], p.R[(size_t)me], &ml, &segs));
+  CHK(dt_add(c, k.s, p.S[(size_t)me], p.R[(size_t)me], &mv));
   if (P == 1) {
-    HIPCHK(launch_moves(ml, k.s));
-    HIPCHK(launch_strided(segs, k.s));
+    HIPCHK(mv.launch(k.s));
     return k.end();
   }
   // scratch slots (16-B aligned) of the strided sends, then of the strided receives
@@ -1860,28 +1901,26 @@ int dt_run(mpjx_comm* c, DtPlan& p, void* stream) {
   for (int j = 0; j < P; j++)
     if (j != me) slot(p.R[(size_t)j], &ro[(size_t)j]);
   if (need) CHK(k.scratch(need));
-  std::vector<StridedSeg> unpack;
+  DtMoves unpack;
   std::vector<Xfer> sends, recvs;
-  MoveList none;
   for (int j = 0; j < P; j++) {
     if (j == me) continue;
     const SideBytes& s = p.S[(size_t)j];
     const SideBytes& r = p.R[(size_t)j];
     if (s.total() > 0) {
       char* at = s.contiguous() ? (char*)(uintptr_t)s.base : c->scratch + so[(size_t)j];
-      if (!s.contiguous()) CHK(dt_add(s, packed_at(at, s.total()), &none, &segs));
+      if (!s.contiguous()) CHK(dt_add(c, k.s, s, packed_at(at, s.total()), &mv));
       sends.push_back({j, at, (size_t)s.total()});
     }
     if (r.total() > 0) {
       char* at = r.contiguous() ? (char*)(uintptr_t)r.base : c->scratch + ro[(size_t)j];
-      if (!r.contiguous()) CHK(dt_add(packed_at(at, r.total()), r, &none, &unpack));
+      if (!r.contiguous()) CHK(dt_add(c, k.s, packed_at(at, r.total()), r, &unpack));
       recvs.push_back({j, at, (size_t)r.total()});
     }
   }
-  HIPCHK(launch_moves(ml, k.s));
-  HIPCHK(launch_strided(segs, k.s));  // the own block and every peer's pack: one launch per table
+  HIPCHK(mv.launch(k.s));  // the own block and every peer's pack: one launch per kernel per table
   CHK(c->tr->exchange(sends, recvs, k.s));
-  HIPCHK(launch_strided(unpack, k.s));
+  HIPCHK(unpack.launch(k.s));
   return k.end();
 }
 
@@ -1905,6 +1944,8 @@ static int alltoallv_dt_entry(mpjx_comm_t c, const void* sendbuf, const int64_t*
   TypeForm st, rt;
   if (!type_form(sendtype, &st)) return fail(MPJX_ERR_ARG, "unknown or freed datatype code %d", sendtype);
   if (!type_form(recvtype, &rt)) return fail(MPJX_ERR_ARG, "unknown or freed datatype code %d", recvtype);
+  if (rt.irr && rt.irr->self_overlap)
+    return fail(MPJX_ERR_ARG, "recvtype %d has blocks that share a byte: it can be sent, not received into", recvtype);
   if (st.base != rt.base)
     return fail(MPJX_ERR_ARG, "sendtype %d (base type %d) and recvtype %d (base type %d) differ in their base type",
                 sendtype, st.base, recvtype, rt.base);

@@ -88,6 +88,46 @@ extern "C" int mpjx_type_vector(int64_t count, int64_t blocklength, int64_t stri
   return type_new(rc, f, err, "Vector", newtype);
 }
 
+// Hvector, Indexed, Hindexed (mpjx_indexed_plan.hpp): any live oldtype
+extern "C" int mpjx_type_hvector(int64_t count, int64_t blocklength, int64_t stride, int oldtype, int* newtype) {
+  if (!newtype) return fail(MPJX_ERR_ARG, "NULL argument");
+  TypeForm old, f;
+  if (!type_form(oldtype, &old)) return fail(MPJX_ERR_ARG, "unknown or freed datatype code %d", oldtype);
+  std::string err;
+  const int rc = hvector_form(count, blocklength, stride, old, &f, &err);
+  return type_new(rc, f, err, "Hvector", newtype);
+}
+
+extern "C" int mpjx_type_indexed(int n, const int64_t* blocklengths, const int64_t* displacements, int oldtype,
+                                 int* newtype) {
+  if (!newtype) return fail(MPJX_ERR_ARG, "NULL argument");
+  TypeForm old, f;
+  if (!type_form(oldtype, &old)) return fail(MPJX_ERR_ARG, "unknown or freed datatype code %d", oldtype);
+  std::string err;
+  const int rc = indexed_form(n, blocklengths, displacements, old, &f, &err);
+  return type_new(rc, f, err, "Indexed", newtype);
+}
+
+extern "C" int mpjx_type_hindexed(int n, const int64_t* blocklengths, const int64_t* displacements, int oldtype,
+                                  int* newtype) {
+  if (!newtype) return fail(MPJX_ERR_ARG, "NULL argument");
+  TypeForm old, f;
+  if (!type_form(oldtype, &old)) return fail(MPJX_ERR_ARG, "unknown or freed datatype code %d", oldtype);
+  std::string err;
+  const int rc = hindexed_form(n, blocklengths, displacements, old, &f, &err);
+  return type_new(rc, f, err, "Hindexed", newtype);
+}
+
+extern "C" int mpjx_type_layout(int type, int64_t* lb, int64_t* ub, int64_t* nblocks, int* regular) {
+  TypeForm f;
+  if (!type_form(type, &f)) return fail(MPJX_ERR_ARG, "unknown or freed datatype code %d", type);
+  if (lb) *lb = f.lb();
+  if (ub) *ub = f.ub();
+  if (nblocks) *nblocks = f.merged_blocks();
+  if (regular) *regular = f.irr ? 0 : 1;
+  return MPJX_SUCCESS;
+}
+
 extern "C" int mpjx_type_free(int type) {
   if (!TypeRegistry::get().release(type)) return fail(MPJX_ERR_ARG, "unknown or freed derived datatype code %d", type);
   return MPJX_SUCCESS;

@@ -294,6 +294,15 @@ struct mpjx_comm {
   // the virtual address of a just-freed 2 MiB page can be served the old page's translation in
   // kernels (the page may belong to another process by then) — DESIGN.md §6, tools/va_alias_probe.cpp.
   std::vector<void*> retired;
+  // The device tables of the irregular datatypes this communicator has launched with (k_indexed), by type
+  // code: uploaded on the call's stream at first use, kept (a code is never reissued, so a freed type's entry
+  // is merely unused) and freed with `retired`. The entry holds the host block list, which so outlives
+  // its upload and every call enqueued with it, whatever mpjx_type_free does.
+  struct IdxTable {
+    const mpjx::IdxEnt* dev;
+    std::shared_ptr<const mpjx::IrrLayout> host;
+  };
+  std::unordered_map<int, IdxTable> idx_tables;
 };
 
 namespace mpjx {

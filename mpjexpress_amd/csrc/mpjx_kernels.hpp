@@ -30,6 +30,7 @@
 
 #include "mpjx_moves_plan.hpp"
 #include "mpjx_ops.hpp"
+#include "mpjx_indexed_plan.hpp"
 #include "mpjx_strided_plan.hpp"
 
 namespace mpjx {
@@ -648,6 +649,10 @@ hipError_t launch_moves(const MoveList& l, hipStream_t s);
 // The packed byte streams of any number of strided moves (mpjx_k_strided.hip): segments planned by
 // plan_strided_seg; more than one table's worth (kStridedMax) runs as consecutive launches on the stream.
 hipError_t launch_strided(const std::vector<StridedSeg>& segs, hipStream_t s);
+
+// The same for moves with an irregular layout on either side (mpjx_k_indexed.hip): segments planned by
+// plan_indexed_seg, their device tables uploaded on `s` or earlier; kIndexedMax segments per launch.
+hipError_t launch_indexed(const std::vector<IndexedSeg>& segs, hipStream_t s);
 
 // IPC device sync (mpjx_ipc.hip): flag slots of the peers (peer[j] = peer j's slot for this rank),
 // this rank's own slots, and the bounded wait's limits; counter = a zeroed device word for the

@@ -8,7 +8,9 @@
 // (TypeForm). A message of `count` items of a type is, per side, a regular two-level layout in bytes
 // (SideBytes): item k at base + k * eb, its block b at + b * sb, bb bytes each. The PACKED form of a
 // message is its blocks in order; a move stores the packed bytes of the source layout in order into the
-// destination layout, so the two block shapes need not agree.
+// destination layout, so the two block shapes need not agree. The irregular types (Hvector, Indexed, Hindexed:
+// mpjx_indexed_plan.hpp) keep a block list instead (IrrLayout); TypeForm and SideBytes carry either kind, and
+// the overlap checks below expand both.
 //   granule  the largest power of two <= 16 B that divides both sides' block bytes, strides, extents and
 //            base addresses: every block of either side starts and ends on a granule of the packed stream,
 //            and every access of one granule is naturally aligned.
@@ -22,6 +24,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -35,14 +38,40 @@ namespace mpjx {
 constexpr int kTypeOk = 0, kTypeErrArg = -1, kTypeErrUnsupported = -6;  // MPJX_SUCCESS / _ERR_ARG / _ERR_UNSUPPORTED
 constexpr int kDerivedBase = 0x10000;                                   // the first derived handle
 
-// In elements of the base type; lb = 0. Contiguous types (nblocks <= 1) have stride == blocklen.
+// One block of an irregular layout, in BYTES: where it starts from the item's origin, and how many packed
+// bytes of the item precede it. The kernel's device table is an array of these (16 B each).
+struct IdxEnt {
+  int64_t off;
+  uint64_t pre;
+};
+
+// The irregular form (Hvector, Indexed, Hindexed: mpjx_indexed_plan.hpp): the merged, non-empty blocks of one
+// item in PACK order (the order of the constructor's arrays, not address order), in bytes. Immutable once
+// made and shared by value-copies of the form, by every layout planned from it and by the communicators'
+// device-table caches, so a call in flight keeps it alive after mpjx_type_free.
+struct IrrLayout {
+  std::vector<IdxEnt> tab;   // never empty; one block is irregular only for its offset (lb > 0)
+  int64_t size = 0;          // packed bytes per item
+  int64_t lb = 0, ub = 0;    // lowest byte and one past the highest byte of an item, from its origin
+  uint64_t amask = 0;        // OR of every block's offset and length and of the extent: the type's part of the granule
+  bool self_overlap = false; // two blocks of one item share a byte: legal to send, MPJX_ERR_ARG to receive into
+  int64_t len(size_t b) const { return (int64_t)((b + 1 < tab.size() ? tab[b + 1].pre : (uint64_t)size) - tab[b].pre); }
+};
+
+// In elements of the base type. Regular (irr == nullptr): nblocks x blocklen at one stride, lb = 0; contiguous
+// types (nblocks <= 1) have stride == blocklen. Irregular: irr holds the blocks; nblocks/blocklen/stride are 0.
 struct TypeForm {
   int base = 0;      // basic code 1..8
   int bsz = 0;       // bytes per base element
   int64_t nblocks = 0, blocklen = 0, stride = 0;
-  int64_t size() const { return nblocks * blocklen; }
-  int64_t extent() const { return nblocks > 0 ? (nblocks - 1) * stride + blocklen : 0; }
-  bool contiguous() const { return nblocks <= 1; }
+  std::shared_ptr<const IrrLayout> irr;
+  int code = 0;      // the code the form was looked up by (type_form); keys the device-table caches
+  int64_t size() const { return irr ? irr->size / bsz : nblocks * blocklen; }
+  int64_t lb() const { return irr ? irr->lb / bsz : 0; }
+  int64_t ub() const { return irr ? irr->ub / bsz : extent(); }
+  int64_t extent() const { return irr ? (irr->ub - irr->lb) / bsz : nblocks > 0 ? (nblocks - 1) * stride + blocklen : 0; }
+  bool contiguous() const { return !irr && nblocks <= 1; }
+  int64_t merged_blocks() const { return irr ? (int64_t)irr->tab.size() : nblocks; }
 };
 
 inline TypeForm contiguous_form(int base, int bsz, int64_t n) {
@@ -75,6 +104,10 @@ inline int vector_form(int64_t count, int64_t blocklength, int64_t stride, const
   if (count < 0 || blocklength < 0) {
     *err = std::string("negative ") + (count < 0 ? "count" : "blocklength");
     return kTypeErrArg;
+  }
+  if (old.irr) {
+    *err = "an irregular oldtype (" + std::to_string(old.irr->tab.size()) + " blocks) is not supported";
+    return kTypeErrUnsupported;
   }
   if (!old.contiguous()) {
     *err = "a strided oldtype (" + std::to_string(old.nblocks) + " blocks of " + std::to_string(old.blocklen) +
@@ -146,6 +179,7 @@ class TypeRegistry {
     const int64_t i = (int64_t)code - kDerivedBase;
     if (i < 0 || i >= (int64_t)slots_.size() || !slots_[(size_t)i].live) return false;
     slots_[(size_t)i].live = false;
+    slots_[(size_t)i].form.irr.reset();  // calls in flight hold their own reference
     return true;
   }
 
@@ -160,28 +194,48 @@ class TypeRegistry {
 
 // Basic, pair and live derived codes
 inline bool type_form(int code, TypeForm* out) {
-  return code >= kDerivedBase ? TypeRegistry::get().find(code, out) : basic_form(code, out);
+  if (!(code >= kDerivedBase ? TypeRegistry::get().find(code, out) : basic_form(code, out))) return false;
+  out->code = code;
+  return true;
 }
 
 // ---- one side of one message, in bytes -------------------------------------------------------------------
 
 // `items` items of a type at byte address `base`: item k at base + k * eb, block b of it at + b * sb, bb
-// bytes per block. A contiguous run is ONE item of ONE block (bb = sb = eb = total).
+// bytes per block. A contiguous run is ONE item of ONE block (bb = sb = eb = total). An irregular layout
+// (irr != nullptr) has item k's block b at base + k * eb + irr->tab[b].off; bb = sb = 0 and nb is its block
+// count. `base` is the item's ORIGIN: an irregular type's lb is not subtracted (GenericPacker).
 struct SideBytes {
   uint64_t base = 0;
   int64_t bb = 0, sb = 0, nb = 0, eb = 0, items = 0;
-  int64_t total() const { return items * nb * bb; }
+  std::shared_ptr<const IrrLayout> irr;
+  int code = 0;  // the irregular type's code
+  int64_t total() const { return irr ? items * irr->size : items * nb * bb; }
   int64_t blocks() const { return items * nb; }
-  bool contiguous() const { return items * nb <= 1; }
+  bool contiguous() const { return !irr && items * nb <= 1; }
+  bool regular() const { return !irr; }
   // The address of packed byte p (numpy-style indexing; the tests' reference for the kernel's mapping)
   uint64_t at(int64_t p) const {
+    if (irr) {
+      const int64_t k = p / irr->size;
+      const uint64_t r = (uint64_t)(p % irr->size);
+      size_t b = 0;
+      while (b + 1 < irr->tab.size() && irr->tab[b + 1].pre <= r) b++;
+      return base + (uint64_t)(k * eb + irr->tab[b].off) + (r - irr->tab[b].pre);
+    }
     const int64_t blk = p / bb, w = p % bb;
     return base + (uint64_t)((blk / nb) * eb + (blk % nb) * sb + w);
   }
   // First and one-past-last byte address touched (first == last when empty)
   void span(uint64_t* lo, uint64_t* hi) const {
     *lo = *hi = base;
-    if (total() > 0) *hi = base + (uint64_t)((items - 1) * eb + (nb - 1) * sb + bb);
+    if (total() <= 0) return;
+    if (irr) {
+      *lo = base + (uint64_t)irr->lb;
+      *hi = base + (uint64_t)((items - 1) * eb + irr->ub);
+    } else {
+      *hi = base + (uint64_t)((items - 1) * eb + (nb - 1) * sb + bb);
+    }
   }
 };
 
@@ -201,11 +255,21 @@ inline bool plan_side(const TypeForm& f, uint64_t buf, int64_t count, int64_t di
   }
   out->base = buf + (uint64_t)(disp * f.bsz);
   if (count == 0 || f.size() == 0) return true;
-  if (count > lim / f.extent()) {
+  if (count > (lim - f.lb()) / f.extent()) {
     *err = std::string(what) + " too large";
     return false;
   }
-  if (f.contiguous() || count * f.nblocks == 1) {
+  if (f.irr && f.irr->tab.size() == 1) {  // one block lb elements in: extent == size, the items abut
+    out->base += (uint64_t)f.irr->tab[0].off;
+    out->bb = out->sb = out->eb = count * f.irr->size;
+    out->nb = out->items = 1;
+  } else if (f.irr) {
+    out->irr = f.irr;
+    out->code = f.code;
+    out->nb = (int64_t)f.irr->tab.size();
+    out->eb = f.extent() * f.bsz;
+    out->items = count;
+  } else if (f.contiguous() || count * f.nblocks == 1) {
     out->bb = out->sb = out->eb = count * f.size() * f.bsz;
     out->nb = out->items = 1;
   } else {
@@ -265,9 +329,12 @@ MPJX_HD inline uint64_t strided_addr(const StridedSide& x, uint32_t q, uint32_t 
 }
 
 // log2 of the largest power of two <= 16 that divides both sides' block bytes, strides, extents and bases
+inline uint64_t side_align_mask(const SideBytes& x) {
+  return x.base | (x.irr ? x.irr->amask : (uint64_t)x.bb | (uint64_t)x.sb | (uint64_t)x.eb);
+}
+// (an irregular side gives its every block offset and length and its extent: mpjx_indexed_plan.hpp)
 inline uint32_t strided_granule_log(const SideBytes& s, const SideBytes& d) {
-  const uint64_t all = s.base | (uint64_t)s.bb | (uint64_t)s.sb | (uint64_t)s.eb | d.base | (uint64_t)d.bb |
-                       (uint64_t)d.sb | (uint64_t)d.eb | 16u;
+  const uint64_t all = side_align_mask(s) | side_align_mask(d) | 16u;
   uint32_t g = 0;
   while (!((all >> g) & 1u)) g++;
   return g;
@@ -369,8 +436,8 @@ inline void expand_blocks(const std::vector<SideBytes>& v, std::vector<AddrBlock
     if (x.total() <= 0) continue;
     for (int64_t k = 0; k < x.items; k++)
       for (int64_t b = 0; b < x.nb; b++) {
-        const uint64_t lo = x.base + (uint64_t)(k * x.eb + b * x.sb);
-        out->push_back(AddrBlock{lo, lo + (uint64_t)x.bb, j});
+        const uint64_t lo = x.base + (uint64_t)(k * x.eb + (x.irr ? x.irr->tab[(size_t)b].off : b * x.sb));
+        out->push_back(AddrBlock{lo, lo + (uint64_t)(x.irr ? x.irr->len((size_t)b) : x.bb), j});
       }
   }
   std::sort(out->begin(), out->end(), [](const AddrBlock& a, const AddrBlock& b) { return a.lo < b.lo; });

@@ -51,15 +51,17 @@ class Datatype:
         self.baseSize = self.np_dtype.itemsize
         self.byteSize = self.baseSize * size
         self.extent = size  # base elements from one item to the next
+        self.lb = 0  # lowest base element of an item from its origin (> 0 only for Hvector/Indexed/Hindexed)
         self.derived = False
 
     @classmethod
     def _derived(cls, code, old, name):
-        """The Datatype of a derived code the library handed out (mpjx_type_contiguous / mpjx_type_vector)."""
-        base, size, extent = ctypes.c_int(), ctypes.c_int64(), ctypes.c_int64()
+        """The Datatype of a derived code the library handed out (mpjx_type_*)."""
+        base, size, extent, lb = ctypes.c_int(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
         _wrap("mpjx_type_info", code, ctypes.byref(base), ctypes.byref(size), ctypes.byref(extent))
+        _wrap("mpjx_type_layout", code, ctypes.byref(lb), None, None, None)
         dt = cls(base.value, name, old.np_dtype, old.torch_dtype_name)
-        dt.size, dt.extent, dt.code, dt.derived = size.value, extent.value, code, True
+        dt.size, dt.extent, dt.lb, dt.code, dt.derived = size.value, extent.value, lb.value, code, True
         dt.byteSize = dt.baseSize * dt.size
         return dt
 
@@ -78,6 +80,35 @@ class Datatype:
         _wrap("mpjx_type_vector", count, blocklength, stride, oldtype.code, ctypes.byref(code))
         return cls._derived(code.value, oldtype, f"Vector({count}, {blocklength}, {stride}, {oldtype.name})")
 
+    @classmethod
+    def Hvector(cls, count, blocklength, stride, oldtype):
+        """Datatype.Hvector (src/mpi/Hvector.java): `count` blocks of `blocklength` items of oldtype, block j
+        starting j * stride BASE elements from the origin. oldtype is any type."""
+        code = ctypes.c_int()
+        _wrap("mpjx_type_hvector", count, blocklength, stride, oldtype.code, ctypes.byref(code))
+        return cls._derived(code.value, oldtype, f"Hvector({count}, {blocklength}, {stride}, {oldtype.name})")
+
+    @classmethod
+    def _indexed(cls, fn, name, blocklengths, displacements, oldtype):
+        bl, ds = [int(x) for x in blocklengths], [int(x) for x in displacements]
+        if len(bl) != len(ds):
+            raise MPIException(f"{name}: {len(bl)} block lengths but {len(ds)} displacements")
+        arr = ctypes.c_int64 * max(len(bl), 1)
+        code = ctypes.c_int()
+        _wrap(fn, len(bl), arr(*bl), arr(*ds), oldtype.code, ctypes.byref(code))
+        return cls._derived(code.value, oldtype, f"{name}({bl}, {ds}, {oldtype.name})")
+
+    @classmethod
+    def Indexed(cls, array_of_blocklengths, array_of_displacements, oldtype):
+        """Datatype.Indexed (src/mpi/Indexed.java): block i is blocklengths[i] items of oldtype starting
+        displacements[i] extents of oldtype from the origin; packed in the arrays' order."""
+        return cls._indexed("mpjx_type_indexed", "Indexed", array_of_blocklengths, array_of_displacements, oldtype)
+
+    @classmethod
+    def Hindexed(cls, array_of_blocklengths, array_of_displacements, oldtype):
+        """Datatype.Hindexed (src/mpi/Hindexed.java): as Indexed, with displacements in BASE elements."""
+        return cls._indexed("mpjx_type_hindexed", "Hindexed", array_of_blocklengths, array_of_displacements, oldtype)
+
     def Commit(self):
         pass
 
@@ -93,10 +124,10 @@ class Datatype:
         return self.extent
 
     def Lb(self):
-        return 0
+        return self.lb
 
     def Ub(self):
-        return self.extent
+        return self.lb + self.extent
 
     def __repr__(self):
         return f"MPI.{self.name}"
@@ -424,7 +455,7 @@ class Intracomm:
         if len(c) < P or len(d) < P:
             raise MPIException(f"{name}: counts or displacements shorter than the communicator")
         arr = ctypes.c_int64 * P
-        span = max([dj + cj * dt.extent for cj, dj in zip(c, d) if cj > 0 and dt.size > 0] or [0])
+        span = max([dj + (cj - 1) * dt.extent + dt.Ub() for cj, dj in zip(c, d) if cj > 0 and dt.size > 0] or [0])
         if span == 0 and buf is None:
             return None, arr(*c), arr(*d)
         if not buf.is_cuda:
