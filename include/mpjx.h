@@ -419,6 +419,55 @@ int mpjx_alltoallv_dt(mpjx_comm_t comm,
                       void *recvbuf, const int64_t *recvcounts, const int64_t *rdispls, int recvtype,
                       void *stream);
 
+/* ---- reductions on derived datatypes ------------------------------------------------------------------
+ * mpjx_reduce / _allreduce / _reduce_scatter / _scan with `type` a basic, pair OR derived code; the other
+ * arguments are their counterparts'. With a basic or pair code each call IS its counterpart.
+ * With a derived code, `count` items of `type` are read from sendbuf and written to recvbuf: item k starts
+ * k * extent after the buffer position and lb is not subtracted, as in mpjx_alltoallv_dt. The reduction is
+ * element-wise over the PACKED sequence of base elements — over (value, index) pairs for a type made of a pair
+ * type, which is what MPJX_MAXLOC / MPJX_MINLOC take — in the combine order of the counterpart on the packed
+ * vectors (the MST tree rooted at `root`, at 0 for Allreduce; FT under MPJX_FLAG_OLD_COLLECTIVES; the Scan
+ * fold; Reduce_scatter's rule by P), so the results are bit-identical to it. Only bytes inside the type's
+ * blocks are written: gaps of recvbuf keep their contents. Reduce: recvbuf is significant at the root only
+ * and may be NULL elsewhere. Reduce_scatter: recvcounts are in items, sendbuf holds their sum, and rank r's
+ * recvcounts[r] items are laid out from recvbuf's own origin. The (op, type) pair is valid exactly when
+ * mpjx_op_check(op, the base or pair type) accepts it. In one call, either every rank passes a basic or pair
+ * code or every rank a derived one. The reference defines no result here (PureIntracomm.Reduce copies
+ * count * size contiguous elements whatever the type): these calls follow MPI.
+ *   MPJX_ERR_ARG: an unknown or freed type; a type whose own blocks share a byte; on one rank, a send layout
+ *   that shares a byte with its receive layout, other than exactly in place (sendbuf == recvbuf;
+ *   Reduce_scatter, whose two layouts differ, has no in-place form) — the exact check and the 65,536-block
+ *   limit of mpjx_alltoallv_dt; where every rank sees every rank's call (multicore ranks on one device,
+ *   2 <= P <= 8), ranks whose base type or packed length differ: there these errors, and a rank's overlap, are
+ *   returned on every rank before anything moves.
+ *   MPJX_ERR_OP_TYPE: as mpjx_op_check, on the base type.
+ *   MPJX_ERR_UNSUPPORTED: MPJX_FLAG_FAITHFUL, MPJX_FLAG_SEND_BIG_ENDIAN or MPJX_FLAG_RECV_BIG_ENDIAN with a
+ *   derived type; 2^32 or more granules in one call.
+ * Asynchronous on `stream`; MPJX_FLAG_BLOCKING is honoured; a failing rank fails its world like every
+ * collective; mpjx_type_free between enqueue and completion changes nothing.
+ * Forms (mpjx_comm_last_dt_form, the last *_dt call of this rank; no reference counterpart, tests read it):
+ *   MPJX_DT_FORM_CONTIGUOUS  a basic or pair code: the contiguous call
+ *   MPJX_DT_FORM_MOVE        one rank: the copy of send into recv through the layouts; in place, nothing
+ *   MPJX_DT_FORM_DIRECT      multicore ranks on one device, 2 <= P <= 8, MPJX_SMP_COPY unset, every rank's
+ *                            type of one normal form: one layout-aware P-way combine kernel launched by rank
+ *                            0 reads every rank's send layout and writes every receive layout in one pass
+ *   MPJX_DT_FORM_PACK        every other world, and ranks whose types differ in form: sendbuf packed into a
+ *                            staging region of the communicator, the contiguous call on the packed vectors,
+ *                            the result unpacked into recvbuf (a contiguous layout skips both passes) */
+#define MPJX_DT_FORM_CONTIGUOUS 1
+#define MPJX_DT_FORM_MOVE 2
+#define MPJX_DT_FORM_DIRECT 3
+#define MPJX_DT_FORM_PACK 4
+int mpjx_reduce_dt(mpjx_comm_t comm, const void *sendbuf, void *recvbuf, int64_t count, int type, int op,
+                   int root, unsigned flags, void *stream);
+int mpjx_allreduce_dt(mpjx_comm_t comm, const void *sendbuf, void *recvbuf, int64_t count, int type,
+                      int op, unsigned flags, void *stream);
+int mpjx_reduce_scatter_dt(mpjx_comm_t comm, const void *sendbuf, void *recvbuf, const int64_t *recvcounts,
+                           int type, int op, unsigned flags, void *stream);
+int mpjx_scan_dt(mpjx_comm_t comm, const void *sendbuf, void *recvbuf, int64_t count, int type, int op,
+                 unsigned flags, void *stream);
+int mpjx_comm_last_dt_form(mpjx_comm_t comm, int *form);
+
 /* ---- host-resident variants (Java heap arrays / mpjbuf payloads) ---------------------------------
  * Synchronous. Buffers are ordinary host memory; the library stages them through device memory.
  * These are what the JNI shim calls with GetPrimitiveArrayCritical / GetDirectBufferAddress

@@ -165,8 +165,12 @@ class Intracomm {
               const Op& op, int root) {
     size_ok<T>(dt);
     // recvbuf: significant at the root; under faithful mode every rank's is written (MST partials)
-    check(mpjx_reduce(c_, sendbuf + sendoffset, (rank_ == root || faithful_) ? recvbuf + recvoffset : nullptr, count,
-                      dt.code, op.opCode, root, flags(), nullptr),
+    // a derived type: the reduction over its packed elements (mpjx_reduce_dt; recvbuf at the root only)
+    check(dt.derived ? mpjx_reduce_dt(c_, sendbuf + sendoffset, rank_ == root ? recvbuf + recvoffset : nullptr, count,
+                                      dt.code, op.opCode, root, flags(), nullptr)
+                     : mpjx_reduce(c_, sendbuf + sendoffset,
+                                   (rank_ == root || faithful_) ? recvbuf + recvoffset : nullptr, count, dt.code,
+                                   op.opCode, root, flags(), nullptr),
           "Reduce");
     sync();
   }
@@ -174,8 +178,8 @@ class Intracomm {
   void Allreduce(const T* sendbuf, int sendoffset, T* recvbuf, int recvoffset, int count, const Datatype& dt,
                  const Op& op) {
     size_ok<T>(dt);
-    check(mpjx_allreduce(c_, sendbuf + sendoffset, recvbuf + recvoffset, count, dt.code, op.opCode, flags(),
-                         nullptr),
+    check((dt.derived ? mpjx_allreduce_dt : mpjx_allreduce)(c_, sendbuf + sendoffset, recvbuf + recvoffset, count, dt.code,
+                                                            op.opCode, flags(), nullptr),
           "Allreduce");
     sync();
   }
@@ -184,15 +188,16 @@ class Intracomm {
                       const Datatype& dt, const Op& op) {
     size_ok<T>(dt);
     std::vector<int64_t> rc = counts(recvcounts);
-    check(mpjx_reduce_scatter(c_, sendbuf + sendoffset, recvbuf + recvoffset, rc.data(), dt.code, op.opCode,
-                              flags(), nullptr),
+    check((dt.derived ? mpjx_reduce_scatter_dt : mpjx_reduce_scatter)(c_, sendbuf + sendoffset, recvbuf + recvoffset,
+                                                                      rc.data(), dt.code, op.opCode, flags(), nullptr),
           "Reduce_scatter");
     sync();
   }
   template <class T>
   void Scan(const T* sendbuf, int sendoffset, T* recvbuf, int recvoffset, int count, const Datatype& dt, const Op& op) {
     size_ok<T>(dt);
-    check(mpjx_scan(c_, sendbuf + sendoffset, recvbuf + recvoffset, count, dt.code, op.opCode, flags(), nullptr),
+    check((dt.derived ? mpjx_scan_dt : mpjx_scan)(c_, sendbuf + sendoffset, recvbuf + recvoffset, count, dt.code,
+                                                  op.opCode, flags(), nullptr),
           "Scan");
     sync();
   }
@@ -346,6 +351,7 @@ class Intracomm {
   void Reduce(const std::vector<T>& sendbuf, int sendoffset, std::vector<T>& recvbuf, int recvoffset, int count,
               const Datatype& dt, const Op& op, int root) {
     size_ok<T>(dt);
+    no_host_dt(dt, "Reduce");
     extent(sendbuf, sendoffset, count, dt.Size());
     const bool all_recv = rank_ == root || faithful_;  // faithful: every rank's recvbuf is written
     if (all_recv) extent(recvbuf, recvoffset, count, dt.Size());
@@ -357,6 +363,7 @@ class Intracomm {
   void Allreduce(const std::vector<T>& sendbuf, int sendoffset, std::vector<T>& recvbuf, int recvoffset, int count,
                  const Datatype& dt, const Op& op) {
     size_ok<T>(dt);
+    no_host_dt(dt, "Allreduce");
     extent(sendbuf, sendoffset, count, dt.Size());
     extent(recvbuf, recvoffset, count, dt.Size());
     check(mpjx_allreduce_host(c_, sendbuf.data() + sendoffset, recvbuf.data() + recvoffset, count, dt.code,
@@ -367,6 +374,7 @@ class Intracomm {
   void Reduce_scatter(const std::vector<T>& sendbuf, int sendoffset, std::vector<T>& recvbuf, int recvoffset,
                       const std::vector<int>& recvcounts, const Datatype& dt, const Op& op) {
     size_ok<T>(dt);
+    no_host_dt(dt, "Reduce_scatter");
     std::vector<int64_t> rc = counts(recvcounts);
     int64_t total = 0;
     for (int64_t x : rc) total += x;
@@ -380,6 +388,7 @@ class Intracomm {
   void Scan(const std::vector<T>& sendbuf, int sendoffset, std::vector<T>& recvbuf, int recvoffset, int count,
             const Datatype& dt, const Op& op) {
     size_ok<T>(dt);
+    no_host_dt(dt, "Scan");
     extent(sendbuf, sendoffset, count, dt.Size());
     extent(recvbuf, recvoffset, count, dt.Size());
     check(mpjx_scan_host(c_, sendbuf.data() + sendoffset, recvbuf.data() + recvoffset, count, dt.code,
@@ -388,6 +397,10 @@ class Intracomm {
   }
 
  private:
+  // the *_host variants take basic and pair types: a derived type reduces device-resident buffers only
+  static void no_host_dt(const Datatype& dt, const char* what) {
+    if (dt.derived) throw MPIException(std::string(what) + ": a derived datatype is provided for device-resident buffers");
+  }
   // the mpiJava calls are blocking: every call returns complete (MPJX_FLAG_BLOCKING)
   unsigned flags() const {
     return (MPI::isOldSelected ? MPJX_FLAG_OLD_COLLECTIVES : 0u) | (faithful_ ? MPJX_FLAG_FAITHFUL : 0u) |

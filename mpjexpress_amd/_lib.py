@@ -83,6 +83,11 @@ def _declare(L):
         "mpjx_type_free": ([c_int], c_int),
         "mpjx_type_info": ([c_int, ctypes.POINTER(c_int), pi64, pi64], c_int),
         "mpjx_alltoallv_dt": ([vp, vp, pi64, pi64, c_int, vp, pi64, pi64, c_int, vp], c_int),
+        "mpjx_reduce_dt": ([vp, vp, vp, c_i64, c_int, c_int, c_int, c_uint, vp], c_int),
+        "mpjx_allreduce_dt": ([vp, vp, vp, c_i64, c_int, c_int, c_uint, vp], c_int),
+        "mpjx_reduce_scatter_dt": ([vp, vp, vp, pi64, c_int, c_int, c_uint, vp], c_int),
+        "mpjx_scan_dt": ([vp, vp, vp, c_i64, c_int, c_int, c_uint, vp], c_int),
+        "mpjx_comm_last_dt_form": ([vp, ctypes.POINTER(c_int)], c_int),
         "mpjx_reduce_host": ([vp, vp, vp, c_i64, c_int, c_int, c_int, c_uint], c_int),
         "mpjx_allreduce_host": ([vp, vp, vp, c_i64, c_int, c_int, c_uint], c_int),
         "mpjx_reduce_scatter_host": ([vp, vp, vp, pi64, c_int, c_int, c_uint], c_int),

@@ -13,6 +13,7 @@
 // The arithmetic order of each algorithm is reproduced per element by the P-way kernels
 // (mpjx_kernels.hpp); the message pattern is replaced by two all-link exchange steps.
 #include "mpjx_internal.hpp"
+#include "mpjx_kernels_dt.hpp"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -2020,6 +2021,361 @@ static int alltoallv_entry(mpjx_comm_t c, const void* sendbuf, const int64_t* se
   return moves_run(c, MV_ALLTOALL, p, type, stream);
 }
 
+// ---- reductions on derived datatypes: mpjx_{reduce,allreduce,reduce_scatter,scan}_dt -----------------------
+// `count` items of ONE type are read from sendbuf and written to recvbuf (item k at k x extent, lb not
+// subtracted: plan_side), reduced element-wise over the packed sequence of base elements (or pairs) in the
+// combine order of the contiguous call on the packed vectors. A basic or pair code IS that contiguous call.
+// A derived code takes one of three engines (mpjx_comm_last_dt_form):
+//   P = 1                     move: the copy of send into recv through the layouts (dt_add: k_moves /
+//                             k_strided / k_indexed); in place, nothing
+//   multicore, one device,    direct: every rank publishes its call (share), rank 0 checks that the ranks
+//   2 <= P <= 8, every type   agree and that no rank's layouts overlap, and launches k_pway_dt
+//   of one form               (mpjx_kernels_dt.hpp) over the one layout all P + Q buffers share; every rank
+//                             fences. One kernel and two rendezvous, like the contiguous direct engine. A
+//                             base-type or packed-length mismatch, or a rank whose send and receive layouts
+//                             overlap, is MPJX_ERR_ARG on every rank before anything moves. Ranks whose types
+//                             have equal signatures but different forms leave together for the pack path.
+//   every other world         pack: sendbuf packed into the communicator's staging region (dtstage) by the
+//                             layout kernels, the contiguous entry point's body on the packed vectors (its
+//                             windows, one-shot, pipeline and flags), the result unpacked into recvbuf. A
+//                             contiguous layout skips both passes.
+// The reference is not followed here: PureIntracomm.Reduce copies count * datatype.size CONTIGUOUS elements
+// (PureIntracomm.java:1937-1938) and the typed workers combine [offset, count) contiguous base elements
+// whatever the type (SumDouble.java:52), so it defines no result for a layout with gaps; these calls follow
+// MPI, as the equal-count moves do.
+
+namespace {
+
+enum RdKind { RD_REDUCE, RD_ALLREDUCE, RD_RSCATTER, RD_SCAN };
+
+// One rank's call; in a direct world the ranks read each other's (share), so it stays in the caller's frame
+// until the fence
+struct RdCall {
+  int kind = RD_ALLREDUCE;
+  const char* send = nullptr;
+  char* recv = nullptr;
+  int64_t items = 0;            // items read from send: count, or the sum of recvcounts
+  int64_t mine = 0;             // items written to recv (0 where recv is not significant)
+  const int64_t* rc = nullptr;  // Reduce_scatter: recvcounts, in items
+  int op = 0, root = 0;
+  unsigned flags = 0;
+  TypeForm f;
+  int eff = 0;      // the element type of the reduction: the base code, or 0x100 | base for a type made of pairs
+  int64_t epi = 1;  // elements of `eff` per item
+  SideBytes S, R;   // the layouts of `items` items at send and of `mine` items at recv (absolute addresses)
+  int bad = MPJX_SUCCESS;  // this rank's own verdict (its layouts overlap), published to the world
+  std::string badmsg;
+};
+
+// The contiguous entry point's body on (s, r): counts in elements of q.eff
+int rd_inner(mpjx_comm* c, const RdCall& q, const void* s, void* r, unsigned flags, void* stream) {
+  const int64_t n = q.items * q.epi;
+  switch (q.kind) {
+    case RD_REDUCE: return reduce_entry(c, s, r, n, q.eff, q.op, q.root, flags, stream);
+    case RD_ALLREDUCE: return allreduce_entry(c, s, r, n, q.eff, q.op, flags, stream);
+    case RD_SCAN: return scan_entry(c, s, r, n, q.eff, q.op, flags, stream);
+    default: break;
+  }
+  if (!c) return fail(MPJX_ERR_ARG, "comm is NULL");
+  if (!q.rc) return reject(c, fail(MPJX_ERR_ARG, "recvcounts is NULL"));
+  std::vector<int64_t> rc((size_t)c->size);
+  for (int j = 0; j < c->size; j++) rc[(size_t)j] = q.rc[j] * q.epi;
+  return reduce_scatter_entry(c, s, r, rc.data(), q.eff, q.op, flags, stream);
+}
+
+int dt_stage(Call& k, size_t bytes) { return grow_device(k.c, &k.c->dtstage, &k.c->dtstage_bytes, bytes, k.s); }
+
+// `x` moved so that its buffer position is `buf` instead of `from`
+SideBytes rebased(const SideBytes& x, const void* from, const void* buf) {
+  SideBytes y = x;
+  y.base = x.base - (uint64_t)(uintptr_t)from + (uint64_t)(uintptr_t)buf;
+  return y;
+}
+
+// One k_pway_dt launch over granules [q0, q0 + nq) of `a.lay`
+int rd_launch(const RdCall& q, int kind, int P, const void* const* in, void* const* out, int nout, int root,
+              PwayDtArgs a, bool vec, hipStream_t s) {
+  for (int p = 0; p < P; p++) a.in[p] = in[p];
+  for (int r = 0; r < nout; r++) a.out[r] = out[r];
+  a.root = root;
+  a.nrep = kind == K_SCAN ? 1 : nout;
+  const hipError_t e = launch_op_dt(q.op, q.eff, kind, P, a, s, vec);
+  if (e == hipErrorNoBinaryForGpu || e == hipErrorInvalidDeviceFunction)
+    return fail(MPJX_ERR_NO_DEVICE, "no gfx950 kernel image for this device: %s", hipGetErrorString(e));
+  if (e != hipSuccess)
+    return fail(MPJX_ERR_HIP, "kernel launch (op %s, type %s on a derived layout, kind %d, P %d): %s", op_name(q.op),
+                type_name(q.eff), kind, P, hipGetErrorString(e));
+  return MPJX_SUCCESS;
+}
+// The MST tree rooted at `root` (two ranks: the root's operand, then the other's, as Combine::mst_o)
+int rd_mst(const RdCall& q, int P, const void* const* in, int root, void* const* out, int nout, const PwayDtArgs& a,
+           bool vec, hipStream_t s) {
+  if (P > 2) return rd_launch(q, K_MST, P, in, out, nout, root, a, vec, s);
+  const void* lst[2] = {in[root], in[1 - root]};
+  return rd_launch(q, K_FOLD, 2, lst, out, nout, 0, a, vec, s);
+}
+// The FT order: in[first], then every other rank ascending (Combine::ft)
+int rd_ft(const RdCall& q, int P, const void* const* in, int first, void* out, const PwayDtArgs& a, bool vec,
+          hipStream_t s) {
+  const void* lst[MAXP];
+  int m = 0;
+  lst[m++] = in[first];
+  for (int i = 0; i < P; i++)
+    if (i != first) lst[m++] = in[i];
+  return rd_launch(q, K_FOLD, P, lst, &out, 1, 0, a, vec, s);
+}
+
+// Rank 0 of a direct world: the k_pway_dt launch or launches of the whole world's call. Every rank's type has
+// rank 0's form and every rank's counts are rank 0's (checked by the caller), so rank 0's own layout, moved
+// to base 0, is the layout of all P send and all receive buffers.
+int rd_direct(Call& k, const RdCall& q, const std::vector<const RdCall*>& all) {
+  mpjx_comm* c = k.c;
+  const int P = c->size;
+  const SideBytes L = rebased(q.S, q.send, nullptr);
+  if (L.total() <= 0) return MPJX_SUCCESS;
+  const bool old = (q.flags & MPJX_FLAG_OLD_COLLECTIVES) != 0;
+  const int64_t size_b = q.f.size() * q.f.bsz, ext_b = q.f.extent() * q.f.bsz;
+  const void* in[MAXP];
+  void* out[MAXP];
+  std::vector<uint64_t> ptrs;
+  int64_t item0 = 0;
+  for (int j = 0; j < P; j++) {
+    in[j] = all[(size_t)j]->send;
+    out[j] = all[(size_t)j]->mine > 0 ? all[(size_t)j]->recv : nullptr;
+    // Reduce_scatter: rank j's pointer moved back so that item item0 lands on its receive buffer's origin
+    if (q.kind == RD_RSCATTER && out[j]) out[j] = (char*)out[j] - item0 * ext_b;
+    if (q.kind == RD_RSCATTER) item0 += q.rc[j];
+    ptrs.push_back((uint64_t)(uintptr_t)in[j]);
+    if (out[j]) ptrs.push_back((uint64_t)(uintptr_t)out[j]);
+  }
+  const int esz = reduce_dt_elem_bytes(q.f);
+  const uint32_t glog = reduce_dt_granule_log(L, esz, ptrs.data(), (int)ptrs.size());
+  const IdxEnt* tab = nullptr;
+  CHK(idx_table(c, q.S, k.s, &tab));
+  PwayDtArgs a{};
+  int64_t ngran = 0;
+  std::string err;
+  const int prc = plan_reduce_dt(L, glog, tab, &a.lay, &ngran, &err);
+  if (prc != kTypeOk) return fail(prc, "%s", err.c_str());
+  a.nq = (uint32_t)ngran;
+  const bool vec = glog == 4;
+  switch (q.kind) {
+    case RD_REDUCE:
+      return old ? rd_ft(q, P, in, q.root, out[q.root], a, vec, k.s)
+                 : rd_mst(q, P, in, q.root, &out[q.root], 1, a, vec, k.s);
+    case RD_SCAN: return rd_launch(q, K_SCAN, P, in, out, P, 0, a, vec, k.s);
+    case RD_RSCATTER: {
+      item0 = 0;
+      for (int r = 0; r < P; item0 += q.rc[r], r++) {
+        if (q.rc[r] <= 0) continue;
+        const DtRange g = reduce_dt_range(item0, q.rc[r], size_b, ext_b, glog);
+        a.q0 = g.q0;
+        a.nq = g.nq;
+        if (old) {  // FT_Reduce_scatter: x_0 folded with x_1 .. x_{P-1}
+          CHK(rd_launch(q, K_FOLD, P, in, &out[r], 1, 0, a, vec, k.s));
+        } else if (P <= 2 && !q.f.pair) {  // the BKT ring at P = 2: own block, then the successor's
+          const void* lst[2] = {in[r], in[(r + 1) % P]};
+          CHK(rd_launch(q, K_FOLD, 2, lst, &out[r], 1, 0, a, vec, k.s));
+        } else {
+          CHK(rd_mst(q, P, in, 0, &out[r], 1, a, vec, k.s));
+        }
+      }
+      return MPJX_SUCCESS;
+    }
+    default: break;
+  }
+  if (!old) return rd_mst(q, P, in, 0, out, P, a, vec, k.s);  // MST(0) -> every rank's recv, one launch
+  // FT_Allreduce: rank r's own fold order for rank r's recv. An in-place rank's recv is an input of every
+  // later fold, so the results go through temporaries (the layout's span each) until all folds are done.
+  bool alias = false;
+  for (int j = 0; j < P; j++) alias = alias || in[j] == out[j];
+  void* res[MAXP];
+  for (int r = 0; r < P; r++) res[r] = out[r];
+  if (alias) {
+    uint64_t lo, hi;
+    L.span(&lo, &hi);
+    const size_t slot = round_up((size_t)(hi - lo) + 16, kAlignBytes);
+    CHK(dt_stage(k, (size_t)P * slot));
+    // 16-B aligned, like every granule's offset where the 16-B form was chosen
+    for (int r = 0; r < P; r++) res[r] = c->dtstage + (size_t)r * slot + (lo & 15u) - lo;
+  }
+  for (int r = 0; r < P; r++) CHK(rd_ft(q, P, in, r, res[r], a, vec, k.s));
+  if (alias) {
+    DtMoves mv;
+    for (int r = 0; r < P; r++) CHK(dt_add(c, k.s, rebased(q.S, q.send, res[r]), rebased(q.S, q.send, out[r]), &mv));
+    HIPCHK(mv.launch(k.s));
+  }
+  return MPJX_SUCCESS;
+}
+
+int rd_run(mpjx_comm* c, RdCall& q, int type, void* stream) {
+  if (!type_form(type, &q.f)) return fail(MPJX_ERR_ARG, "unknown or freed datatype code %d", type);
+  if (type < kDerivedBase) {  // a basic or pair code: the contiguous call itself
+    q.eff = type;
+    q.epi = 1;
+    if (c) c->dt_form = MPJX_DT_FORM_CONTIGUOUS;
+    return rd_inner(c, q, q.send, q.recv, q.flags, stream);
+  }
+  q.eff = q.f.pair ? (0x100 | q.f.base) : q.f.base;
+  q.epi = q.f.size() / (q.f.pair ? 2 : 1);
+  {
+    const int orc = mpjx_op_check(q.op, q.eff);
+    if (orc != MPJX_SUCCESS) return reject(c, orc);
+  }
+  if (q.flags & MPJX_FLAG_FAITHFUL)
+    return reject(c, fail(MPJX_ERR_UNSUPPORTED, "MPJX_FLAG_FAITHFUL with the derived datatype %d: the reference "
+                                                "defines no result for a reduction on a layout", type));
+  if (q.flags & (MPJX_FLAG_SEND_BIG_ENDIAN | MPJX_FLAG_RECV_BIG_ENDIAN))
+    return reject(c, fail(MPJX_ERR_UNSUPPORTED, "big-endian buffers (flags 0x%x) with the derived datatype %d",
+                          q.flags, type));
+  if (q.f.irr && q.f.irr->self_overlap)
+    return reject(c, fail(MPJX_ERR_ARG, "datatype %d has blocks that share a byte: a reduction receives into it", type));
+  if (!c) return fail(MPJX_ERR_ARG, "comm is NULL");
+  const int P = c->size, me = c->rank;
+  const int64_t count = q.mine;  // as passed (Reduce_scatter: unused)
+  if (q.kind == RD_REDUCE) CHK(check_root(c, q.root));
+  if (q.kind == RD_RSCATTER) {
+    if (!q.rc) return reject(c, fail(MPJX_ERR_ARG, "recvcounts is NULL"));
+    q.items = 0;
+    for (int j = 0; j < P; j++) {
+      if (q.rc[j] < 0) return reject(c, fail(MPJX_ERR_ARG, "recvcounts[%d] = %lld is negative", j, (long long)q.rc[j]));
+      q.items += q.rc[j];
+    }
+    q.mine = q.rc[me];
+  } else {
+    if (count < 0) return reject(c, fail(MPJX_ERR_ARG, "negative count %lld", (long long)count));
+    q.items = count;
+    q.mine = (q.kind == RD_REDUCE && me != q.root) ? 0 : count;
+  }
+  std::string err;
+  if (!plan_side(q.f, (uint64_t)(uintptr_t)q.send, q.items, 0, &q.S, &err, "count") ||
+      !plan_side(q.f, (uint64_t)(uintptr_t)q.recv, q.mine, 0, &q.R, &err, "count"))
+    return reject(c, fail(MPJX_ERR_ARG, "%s (datatype %d)", err.c_str(), type));
+  const int64_t sb = q.S.total(), rb = q.R.total();
+  if (rb == 0) q.mine = 0;
+  if ((sb > 0 && !q.send) || (rb > 0 && !q.recv))
+    return reject(c, fail(MPJX_ERR_ARG, "NULL buffer with %lld items of datatype %d", (long long)q.items, type));
+  CHK(check_bufs(c, sb > 0 ? q.send : nullptr, rb > 0 ? q.recv : nullptr));
+  // exactly in place (the same position, so the same layout on both sides) is the one overlap allowed;
+  // Reduce_scatter's two layouts differ beyond one rank, so there it has no in-place form
+  if (sb > 0 && rb > 0 && !((q.kind != RD_RSCATTER || P == 1) && (const char*)q.recv == q.send)) {
+    int a = 0, b = 0;
+    if (strided_overlap({q.S}, {q.R}, &a, &b) == kSendRecvOverlap) {
+      q.bad = MPJX_ERR_ARG;
+      char msg[256];
+      snprintf(msg, sizeof msg, "rank %d: the layouts of datatype %d at sendbuf %p and at recvbuf %p share a byte "
+               "(only sendbuf == recvbuf is in place%s)", me, type, (const void*)q.send, (void*)q.recv,
+               q.kind == RD_RSCATTER ? "; Reduce_scatter has no in-place form" : "");
+      q.badmsg = msg;
+    }
+  }
+  const bool blocking = (q.flags & MPJX_FLAG_BLOCKING) != 0;
+  Call k;
+  if (P == 1) {
+    c->dt_form = MPJX_DT_FORM_MOVE;
+    if (q.bad) return fail(q.bad, "%s", q.badmsg.c_str());
+    CHK(k.begin(c, stream, q.eff));
+    k.blocking = blocking;
+    if (rb > 0 && (const char*)q.recv != q.send) {
+      DtMoves mv;
+      CHK(dt_add(c, k.s, q.S, q.R, &mv));
+      HIPCHK(mv.launch(k.s));
+    }
+    CHK(k.end());
+    return finish_blocking(c, q.flags, stream);
+  }
+  auto* t = dynamic_cast<SmpTransport*>(c->tr.get());
+  if (P <= MAXP && t && smp_direct(c) && t->single()) {
+    CHK(k.begin(c, stream, q.eff));
+    k.blocking = blocking;
+    std::vector<std::vector<const void*>> shared;
+    CHK(t->share(std::vector<const void*>{&q}, k.s, &shared, true));
+    std::vector<const RdCall*> all((size_t)P);
+    for (int j = 0; j < P; j++) all[(size_t)j] = (const RdCall*)shared[(size_t)j][0];
+    // every rank reads every rank's call and reaches the same verdict
+    int bad = MPJX_SUCCESS;
+    char msg[384] = "";
+    bool same = true;
+    for (int j = 0; j < P && !bad; j++) {
+      const RdCall& x = *all[(size_t)j];
+      const RdCall& z = *all[0];
+      if (x.bad) {
+        bad = x.bad;
+        snprintf(msg, sizeof msg, "%s", x.badmsg.c_str());
+      } else if (x.eff != z.eff) {
+        bad = MPJX_ERR_ARG;
+        snprintf(msg, sizeof msg, "rank %d reduces base type %s but rank 0 base type %s", j, type_name(x.eff), type_name(z.eff));
+      } else if (x.items * x.epi != z.items * z.epi) {
+        bad = MPJX_ERR_ARG;
+        snprintf(msg, sizeof msg, "rank %d reduces %lld elements but rank 0 reduces %lld", j, (long long)(x.items * x.epi),
+                 (long long)(z.items * z.epi));
+      } else if (x.kind != z.kind || x.op != z.op || (x.kind == RD_REDUCE && x.root != z.root) ||
+                 ((x.flags ^ z.flags) & MPJX_FLAG_OLD_COLLECTIVES)) {
+        bad = MPJX_ERR_ARG;
+        snprintf(msg, sizeof msg, "rank %d and rank 0 differ in the collective, its op, root or flags", j);
+      }
+      for (int r = 0; r < P && !bad && x.kind == RD_RSCATTER; r++)
+        if (x.rc[r] * x.epi != z.rc[r] * z.epi) {
+          bad = MPJX_ERR_ARG;
+          snprintf(msg, sizeof msg, "rank %d gives rank %d %lld elements but rank 0 gives it %lld", j, r,
+                   (long long)(x.rc[r] * x.epi), (long long)(z.rc[r] * z.epi));
+        }
+      same = same && x.items == z.items && same_form(x.f, z.f);
+    }
+    if (bad || !same) {
+      (void)t->fence(k.s, true);  // every rank has read every call before any rank's frame goes
+      if (bad) return fail(bad, "%s", msg);
+      CHK(k.end());
+    } else {
+      c->dt_form = MPJX_DT_FORM_DIRECT;
+      if (me == 0) DCHK(rd_direct(k, q, all));
+      CHK(t->fence(k.s, true, false, blocking));
+      CHK(k.end());
+      return finish_blocking(c, q.flags, stream);
+    }
+  } else if (q.bad) {
+    return reject(c, fail(q.bad, "%s", q.badmsg.c_str()));
+  }
+  // the pack path
+  c->dt_form = MPJX_DT_FORM_PACK;
+  CHK(k.begin(c, stream, q.eff));
+  const bool pack = sb > 0 && !q.S.contiguous(), unpack = rb > 0 && !q.R.contiguous();
+  const size_t shalf = pack ? round_up((size_t)sb, kAlignBytes) : 0;
+  if (pack || unpack) CHK(dt_stage(k, shalf + (unpack ? round_up((size_t)rb, kAlignBytes) : 0)));
+  const char* ps = pack ? c->dtstage : sb > 0 ? (const char*)(uintptr_t)q.S.base : q.send;
+  char* pr = unpack ? c->dtstage + shalf : rb > 0 ? (char*)(uintptr_t)q.R.base : nullptr;
+  if (pack) {
+    DtMoves mv;
+    CHK(dt_add(c, k.s, q.S, packed_at(ps, sb), &mv));
+    HIPCHK(mv.launch(k.s));
+  }
+  CHK(k.end());
+  CHK(rd_inner(c, q, ps, pr, q.flags & ~MPJX_FLAG_BLOCKING, k.s));
+  if (unpack) {
+    DtMoves mv;
+    CHK(dt_add(c, k.s, packed_at(pr, rb), q.R, &mv));
+    HIPCHK(mv.launch(k.s));
+  }
+  CHK(k.end());
+  return finish_blocking(c, q.flags, stream);
+}
+
+int rd_call(mpjx_comm* c, int kind, const void* sendbuf, void* recvbuf, int64_t count, const int64_t* recvcounts,
+            int type, int op, int root, unsigned flags, void* stream) {
+  RdCall q;
+  q.kind = kind;
+  q.send = (const char*)sendbuf;
+  q.recv = (char*)recvbuf;
+  q.items = q.mine = count;
+  q.rc = recvcounts;
+  q.op = op;
+  q.root = root;
+  q.flags = flags;
+  return rd_run(c, q, type, stream);
+}
+
+}  // namespace
+
 // The C-ABI entry points. A call that fails leaves this rank out of step with its peers (it skipped the
 // collective, or stopped between two of its transport steps): `ended` tells the transport
 // (Transport::call_failed). Multicore and IPC worlds are marked failed, so peers waiting for this rank
@@ -2101,6 +2457,33 @@ extern "C" int mpjx_reduce_scatter(mpjx_comm_t c, const void* sendbuf, void* rec
 extern "C" int mpjx_scan(mpjx_comm_t c, const void* sendbuf, void* recvbuf, int64_t count, int type, int op,
                          unsigned flags, void* stream) {
   return ended(c, scan_entry(c, sendbuf, recvbuf, count, type, op, flags, stream));
+}
+
+extern "C" int mpjx_reduce_dt(mpjx_comm_t c, const void* sendbuf, void* recvbuf, int64_t count, int type, int op,
+                              int root, unsigned flags, void* stream) {
+  return ended(c, rd_call(c, RD_REDUCE, sendbuf, recvbuf, count, nullptr, type, op, root, flags, stream));
+}
+
+extern "C" int mpjx_allreduce_dt(mpjx_comm_t c, const void* sendbuf, void* recvbuf, int64_t count, int type, int op,
+                                 unsigned flags, void* stream) {
+  return ended(c, rd_call(c, RD_ALLREDUCE, sendbuf, recvbuf, count, nullptr, type, op, 0, flags, stream));
+}
+
+extern "C" int mpjx_reduce_scatter_dt(mpjx_comm_t c, const void* sendbuf, void* recvbuf, const int64_t* recvcounts,
+                                      int type, int op, unsigned flags, void* stream) {
+  return ended(c, rd_call(c, RD_RSCATTER, sendbuf, recvbuf, 0, recvcounts, type, op, 0, flags, stream));
+}
+
+extern "C" int mpjx_scan_dt(mpjx_comm_t c, const void* sendbuf, void* recvbuf, int64_t count, int type, int op,
+                            unsigned flags, void* stream) {
+  return ended(c, rd_call(c, RD_SCAN, sendbuf, recvbuf, count, nullptr, type, op, 0, flags, stream));
+}
+
+extern "C" int mpjx_comm_last_dt_form(mpjx_comm_t c, int* form) {
+  COMM_ARG(c);
+  if (!form) return fail(MPJX_ERR_ARG, "NULL argument");
+  *form = c->dt_form;
+  return MPJX_SUCCESS;
 }
 
 extern "C" int mpjx_allreduce_host(mpjx_comm_t c, const void* sendbuf, void* recvbuf, int64_t count, int type, int op,

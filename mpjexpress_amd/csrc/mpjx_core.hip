@@ -76,6 +76,7 @@ extern "C" int mpjx_type_contiguous(int64_t count, int oldtype, int* newtype) {
   if (!type_form(oldtype, &old)) return fail(MPJX_ERR_ARG, "unknown or freed datatype code %d", oldtype);
   std::string err;
   const int rc = contiguous_of(count, old, &f, &err);
+  f.pair = old.pair;
   return type_new(rc, f, err, "Contiguous", newtype);
 }
 
@@ -85,6 +86,7 @@ extern "C" int mpjx_type_vector(int64_t count, int64_t blocklength, int64_t stri
   if (!type_form(oldtype, &old)) return fail(MPJX_ERR_ARG, "unknown or freed datatype code %d", oldtype);
   std::string err;
   const int rc = vector_form(count, blocklength, stride, old, &f, &err);
+  f.pair = old.pair;
   return type_new(rc, f, err, "Vector", newtype);
 }
 
@@ -95,6 +97,7 @@ extern "C" int mpjx_type_hvector(int64_t count, int64_t blocklength, int64_t str
   if (!type_form(oldtype, &old)) return fail(MPJX_ERR_ARG, "unknown or freed datatype code %d", oldtype);
   std::string err;
   const int rc = hvector_form(count, blocklength, stride, old, &f, &err);
+  f.pair = old.pair;
   return type_new(rc, f, err, "Hvector", newtype);
 }
 
@@ -105,6 +108,7 @@ extern "C" int mpjx_type_indexed(int n, const int64_t* blocklengths, const int64
   if (!type_form(oldtype, &old)) return fail(MPJX_ERR_ARG, "unknown or freed datatype code %d", oldtype);
   std::string err;
   const int rc = indexed_form(n, blocklengths, displacements, old, &f, &err);
+  f.pair = old.pair;
   return type_new(rc, f, err, "Indexed", newtype);
 }
 
@@ -115,6 +119,7 @@ extern "C" int mpjx_type_hindexed(int n, const int64_t* blocklengths, const int6
   if (!type_form(oldtype, &old)) return fail(MPJX_ERR_ARG, "unknown or freed datatype code %d", oldtype);
   std::string err;
   const int rc = hindexed_form(n, blocklengths, displacements, old, &f, &err);
+  f.pair = old.pair;
   return type_new(rc, f, err, "Hindexed", newtype);
 }
 

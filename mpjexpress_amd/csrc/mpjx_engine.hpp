@@ -289,6 +289,13 @@ struct mpjx_comm {
   // the form the last *_host call took (mpjx_comm_last_host_form): 1 staged through device buffers
   // (chunk pipeline), 2 host-direct (the kernel loads and stores the page-locked host buffers); 0 none
   int host_form = 0;
+  // the reductions on derived datatypes (mpjx_*_dt): the form the last one took (mpjx_comm_last_dt_form,
+  // MPJX_DT_FORM_*; 0 none yet), and their staging region — the packed send and receive vectors of the pack
+  // path, the temporaries of the direct FT Allreduce — apart from `scratch`, which the contiguous bodies
+  // carve; grown on demand and kept until the communicator is destroyed, as hstage is
+  int dt_form = 0;
+  char* dtstage = nullptr;
+  size_t dtstage_bytes = 0;
   // Device buffers outgrown during the communicator's life, freed only by mpjx_comm_destroy. Growing
   // never frees-then-reallocates: on a GPU shared by several processes, a hipMalloc that gets back
   // the virtual address of a just-freed 2 MiB page can be served the old page's translation in

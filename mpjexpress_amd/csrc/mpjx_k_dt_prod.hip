@@ -1,0 +1,19 @@
+// mpjx_k_dt_prod.hip — k_pway_dt instantiations for the PROD functors (one op family per translation unit, as
+// mpjx_k_prod.hip). Type codes are mpi.Datatype base types (src/mpi/Datatype.java:57-66).
+#include "mpjx_kernels_dt.hpp"
+
+namespace mpjx {
+hipError_t launch_prod_dt(int type, int kind, int P, const PwayDtArgs& a, hipStream_t s, bool vec) {
+  switch (type) {
+    case 1: /* BYTE */ return launch_functor_dt<Prod<uint8_t>>(kind, P, a, s, vec);
+    case 2: /* CHAR */ return launch_functor_dt<Prod<uint16_t>>(kind, P, a, s, vec);
+    case 3: /* SHORT */ return launch_functor_dt<Prod<uint16_t>>(kind, P, a, s, vec);
+    case 5: /* INT */ return launch_functor_dt<Prod<uint32_t>>(kind, P, a, s, vec);
+    case 6: /* LONG */ return launch_functor_dt<Prod<uint64_t>>(kind, P, a, s, vec);
+    case 7: /* FLOAT */ return launch_functor_dt<Prod<float>>(kind, P, a, s, vec);
+    case 8: /* DOUBLE */ return launch_functor_dt<Prod<double>>(kind, P, a, s, vec);
+  }
+  return hipErrorInvalidValue;
+}
+
+}  // namespace mpjx

@@ -66,6 +66,8 @@ struct TypeForm {
   int64_t nblocks = 0, blocklen = 0, stride = 0;
   std::shared_ptr<const IrrLayout> irr;
   int code = 0;      // the code the form was looked up by (type_form); keys the device-table caches
+  bool pair = false; // made of (value, index) pair items: what MAXLOC / MINLOC reduce (the type constructors of
+                     // mpjx_core.hip hand it on from the oldtype; the moves do not read it)
   int64_t size() const { return irr ? irr->size / bsz : nblocks * blocklen; }
   int64_t lb() const { return irr ? irr->lb / bsz : 0; }
   int64_t ub() const { return irr ? irr->ub / bsz : extent(); }
@@ -92,6 +94,7 @@ inline bool basic_form(int code, TypeForm* out) {
   const int b = code & 0xff;
   if ((code & ~0xff) == 0x100 && (b == 3 || (b >= 5 && b <= 8))) {
     *out = contiguous_form(b, bytes[b], 2);
+    out->pair = true;
     return true;
   }
   return false;

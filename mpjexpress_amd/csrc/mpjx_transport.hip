@@ -563,6 +563,7 @@ extern "C" int mpjx_comm_destroy(mpjx_comm_t c) {
   for (void* p : c->retired) (void)hipFree(p);
   if (c->scratch) (void)hipFree(c->scratch);
   if (c->hstage) (void)hipFree(c->hstage);
+  if (c->dtstage) (void)hipFree(c->dtstage);
   for (hipStream_t hs : {c->h2d, c->d2h})
     if (hs) {
       (void)hipStreamSynchronize(hs);

@@ -8,6 +8,7 @@ reference's own programs (e.g. test/mpi/ccl/allreduce.java):
     comm.Allreduce(send, soff, recv, roff, count, datatype, op)          src/mpi/Intracomm.java:787-793
     comm.Reduce_scatter(send, soff, recv, roff, recvcounts, datatype, op) src/mpi/Intracomm.java:833-840
     comm.Scan(send, soff, recv, roff, count, datatype, op)               src/mpi/Intracomm.java:879-885
+        (a derived datatype on device tensors: the mpjx_*_dt calls, element-wise over the packed sequence)
     comm.Bcast(buf, off, count, datatype, root), comm.Barrier(), comm.Rank(), comm.Size()
     comm.Allgather / Allgatherv / Gatherv / Scatterv / Alltoall / Alltoallv(sendbuf, sendoffset, sendcount[s],
         [sdispls,] sendtype, recvbuf, recvoffset, recvcount[s], [rdispls,] recvtype[, root])
@@ -211,6 +212,26 @@ def _dev_ptr(buf, off, dt, need):
     return buf.data_ptr() + off * dt.baseSize
 
 
+def _dev_ptr_dt(buf, off, dt, count):
+    """Device address of base element `off` for `count` items of the derived type dt: the buffer must hold
+    the layout's true span ((count - 1) extents and one ub), not count * size elements."""
+    span = (count - 1) * dt.extent + dt.Ub() if count > 0 and dt.size > 0 else 0
+    if not buf.is_cuda:
+        raise MPIException("torch tensor buffers must be on a GPU device")
+    if not buf.is_contiguous():
+        raise MPIException("buffer must be contiguous")
+    if buf.element_size() != dt.baseSize:
+        raise MPIException(f"buffer element size {buf.element_size()} does not match {dt}")
+    if count < 0 or off < 0 or off + span > buf.numel():
+        raise MPIException(f"offset {off} + layout span {span} of {count} x {dt} exceeds buffer length {buf.numel()}")
+    return buf.data_ptr() + off * dt.baseSize
+
+
+def _no_host_dt(name, dt):
+    raise MPIException(f"{name}: the derived datatype {dt} is provided for device-resident buffers "
+                       "(the *_host variants take basic and pair types)")
+
+
 def _host_ptr(buf, off, dt, need):
     """Host address of base element `off` (numpy arrays of the base type, or of structured pairs)."""
     if not isinstance(buf, np.ndarray) or not buf.flags.c_contiguous:
@@ -367,7 +388,15 @@ class Intracomm:
         """recvbuf is significant at the root; with faithful=True every rank's recvbuf is left as
         PureIntracomm leaves it (MST: the rank's sub-tree partial, FT: its own send copy)."""
         is_root = self._rank == root
-        if _is_torch(sendbuf):
+        if datatype.derived:
+            if not _is_torch(sendbuf):
+                _no_host_dt("Reduce", datatype)
+            self._sync_in(sendbuf)
+            sp = _dev_ptr_dt(sendbuf, sendoffset, datatype, count)
+            rp = _dev_ptr_dt(recvbuf, recvoffset, datatype, count) if is_root else None
+            _wrap("mpjx_reduce_dt", self._h, sp, rp, count, datatype.code, op.opCode, root, self.flags(), None)
+            self._sync_out()
+        elif _is_torch(sendbuf):
             self._sync_in(sendbuf)
             sp = _dev_ptr(sendbuf, sendoffset, datatype, count)
             rp = _dev_ptr(recvbuf, recvoffset, datatype, count) if (is_root or self.faithful) else None
@@ -381,7 +410,15 @@ class Intracomm:
                   self.flags())
 
     def Allreduce(self, sendbuf, sendoffset, recvbuf, recvoffset, count, datatype, op):
-        if _is_torch(sendbuf):
+        if datatype.derived:
+            if not _is_torch(sendbuf):
+                _no_host_dt("Allreduce", datatype)
+            self._sync_in(sendbuf, recvbuf)
+            sp = _dev_ptr_dt(sendbuf, sendoffset, datatype, count)
+            rp = _dev_ptr_dt(recvbuf, recvoffset, datatype, count)
+            _wrap("mpjx_allreduce_dt", self._h, sp, rp, count, datatype.code, op.opCode, self.flags(), None)
+            self._sync_out()
+        elif _is_torch(sendbuf):
             self._sync_in(sendbuf, recvbuf)
             sp = _dev_ptr(sendbuf, sendoffset, datatype, count)
             rp = _dev_ptr(recvbuf, recvoffset, datatype, count)
@@ -400,7 +437,15 @@ class Intracomm:
             raise MPIException("recvcounts shorter than the communicator")
         rc = (ctypes.c_int64 * self._size)(*counts)
         total, mine = sum(counts), counts[self._rank]  # datatype elements
-        if _is_torch(sendbuf):
+        if datatype.derived:
+            if not _is_torch(sendbuf):
+                _no_host_dt("Reduce_scatter", datatype)
+            self._sync_in(sendbuf, recvbuf)
+            sp = _dev_ptr_dt(sendbuf, sendoffset, datatype, total)
+            rp = _dev_ptr_dt(recvbuf, recvoffset, datatype, mine)
+            _wrap("mpjx_reduce_scatter_dt", self._h, sp, rp, rc, datatype.code, op.opCode, self.flags(), None)
+            self._sync_out()
+        elif _is_torch(sendbuf):
             self._sync_in(sendbuf, recvbuf)
             sp = _dev_ptr(sendbuf, sendoffset, datatype, total)
             rp = _dev_ptr(recvbuf, recvoffset, datatype, mine)
@@ -414,7 +459,15 @@ class Intracomm:
                   self.flags())
 
     def Scan(self, sendbuf, sendoffset, recvbuf, recvoffset, count, datatype, op):
-        if _is_torch(sendbuf):
+        if datatype.derived:
+            if not _is_torch(sendbuf):
+                _no_host_dt("Scan", datatype)
+            self._sync_in(sendbuf, recvbuf)
+            sp = _dev_ptr_dt(sendbuf, sendoffset, datatype, count)
+            rp = _dev_ptr_dt(recvbuf, recvoffset, datatype, count)
+            _wrap("mpjx_scan_dt", self._h, sp, rp, count, datatype.code, op.opCode, self.flags(), None)
+            self._sync_out()
+        elif _is_torch(sendbuf):
             self._sync_in(sendbuf, recvbuf)
             sp = _dev_ptr(sendbuf, sendoffset, datatype, count)
             rp = _dev_ptr(recvbuf, recvoffset, datatype, count)

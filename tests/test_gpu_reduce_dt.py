@@ -1,0 +1,331 @@
+"""GPU: Reduce, Allreduce, Reduce_scatter and Scan on derived datatypes, in-process on device 0: the one-rank
+move through the C ABI, the layout-direct kernel k_pway_dt in one-device multicore worlds of 2, 3, 5 and 8 rank
+threads, the pack path (ranks whose layouts differ, P = 9, MPJX_SMP_COPY=1) and the errors every rank must
+return before anything moves. Every case asserts the form the call took (mpjx_comm_last_dt_form), so the pack
+path cannot stand in for a broken kernel. The expectation is tests/reduce_dt_cases.py's: the oracle on the
+packed vectors, scattered into a sentinel-filled buffer that is compared whole.
+
+The kernel's tile is 256 lanes x Unroll<P> granules (4 at P = 2, 2 at P = 3 and 4, 1 above; one granule per
+lane for 8- and 16-bit types in the 16-B form at P >= 3): at P = 3 that is 512 granules, so the TILES cases
+below hold three full tiles and a partial one in the element form (1636 INT elements) and in the 16-B form
+(1620 granules of two DOUBLEs)."""
+import ctypes
+import os
+import threading
+
+import numpy as np
+import pytest
+
+import oracle as O
+import reduce_dt_cases as RC
+import strided_cases as SC
+from mpjexpress_amd import _lib, mpi
+from mpjexpress_amd.mpi import MPI, Datatype, MPIException
+from reduce_dt_cases import Case
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+
+def run_ranks(comms, fn, limit=60):
+    """fn(comm) on one thread per rank under a time limit; returns (results, errors) per rank."""
+    P = len(comms)
+    out, err = [None] * P, [None] * P
+
+    def body(r):
+        try:
+            torch.cuda.set_device(0)
+            out[r] = fn(comms[r])
+        except BaseException as e:  # noqa: BLE001
+            err[r] = e
+    ts = [threading.Thread(target=body, args=(r,), daemon=True) for r in range(P)]
+    for t in ts:
+        t.start()
+    for t in ts:
+        t.join(timeout=limit)
+    assert not any(t.is_alive() for t in ts), "a rank hung"
+    return out, err
+
+
+def free(comms):
+    for c in comms:
+        c.Free()
+
+
+def run_world(P, cases, form, old=False):
+    """Every case on one world of P rank threads; each must take `form` and match its expectation."""
+    assert all(c.old == old for c in cases)
+    data = [RC.expected(c, P) for c in cases]
+    comms = mpi.smp_world(P, [0] * P)
+    was = MPI.isOldSelected
+    MPI.isOldSelected = old
+
+    def body(c):
+        types, bad = {}, []
+        try:
+            for case, d in zip(cases, data):
+                bad += RC.run_rank(torch, c, case, d, form, types)
+        finally:
+            for t in types.values():
+                t.Free()
+        return bad
+    try:
+        out, err = run_ranks(comms, body)
+        assert not any(err), err
+        bad = [m for r in out for m in r]
+        assert not bad, bad[:6]
+    finally:
+        MPI.isOldSelected = was
+        free(comms)
+
+
+BLOCKS = ("V", 9, 4, 10)            # 32-B blocks 80 B apart: the 16-B form at an aligned base
+COLUMN = ("V", 33, 1, 17)           # a column of a 33 x 17 matrix
+ODD = ("V", 5, 3, 7)
+RI = ("H", (2, 2, 2), (1, 11, 5))   # lb = 1, blocks that go back and forth
+SI = ("I", (3, 1, 2), (8, 0, 4))    # a displaced first block
+
+
+def ragged(P):
+    return [(2, 0, 3, 1)[r % 4] for r in range(P)]
+
+
+def direct_cases(P):
+    return [
+        Case("allreduce", "DOUBLE", BLOCKS, 2, O.SUM, soff=0, roff=0, seed=1),   # the 16-B width
+        Case("allreduce", "DOUBLE", BLOCKS, 2, O.SUM, soff=1, roff=1, seed=2),   # one element further: the element width
+        Case("allreduce", "FLOAT", COLUMN, 1, O.SUM, soff=3, roff=5, seed=3),
+        Case("allreduce", "FLOAT", ODD, 3, O.MAX, soff=1, roff=2, seed=4),       # NaN and +-0 among the specials
+        Case("allreduce", "BYTE", ODD, 2, O.BXOR, soff=3, roff=1, seed=5),       # odd addresses
+        Case("allreduce", "DOUBLE2", ("V", 3, 2, 4), 2, O.MAXLOC, soff=2, roff=0, seed=6),
+        Case("reduce", "INT", ("V", 6, 2, 5), 3, O.SUM, soff=1, roff=2, root=0, seed=7),
+        Case("reduce", "INT", ("V", 6, 2, 5), 3, O.SUM, soff=1, roff=2, root=P - 1, seed=8),
+        Case("scan", "INT", ("V", 6, 2, 5), 3, O.PROD, soff=1, roff=0, seed=9),
+        Case("reduce_scatter", "INT", ("V", 4, 3, 7), ragged(P), O.BAND, soff=1, roff=3, seed=10),
+        Case("allreduce", "INT", RI, 3, O.SUM, soff=1, roff=2, seed=11),
+        Case("scan", "DOUBLE", SI, 2, O.MIN, soff=0, roff=0, seed=12),
+        Case("reduce_scatter", "INT", RI, ragged(P), O.MAX, soff=2, roff=0, seed=13),
+        Case("allreduce", "INT", ODD, 2, O.SUM, soff=1, inplace=range(P), seed=14),  # every rank in place
+    ]
+
+
+@pytest.mark.parametrize("P", [2, 3, 5, 8])
+def test_direct_form(P):
+    run_world(P, direct_cases(P), RC.FORM_DIRECT)
+
+
+@pytest.mark.parametrize("P", [2, 3, 5, 8])
+def test_direct_form_old_collectives(P):
+    """MPJX_FLAG_OLD_COLLECTIVES: FT Allreduce with one rank in place (P folds through temporaries), without
+    one, and FT Reduce."""
+    run_world(P, [
+        Case("allreduce", "DOUBLE", BLOCKS, 2, O.SUM, soff=0, old=True, inplace=[1], seed=21),
+        Case("allreduce", "FLOAT", ODD, 3, O.SUM, soff=1, roff=2, old=True, seed=22),
+        Case("allreduce", "INT", RI, 3, O.SUM, soff=1, old=True, inplace=[0], seed=23),
+        Case("reduce", "DOUBLE", ODD, 2, O.PROD, soff=1, roff=0, root=P - 1, old=True, seed=24),
+        Case("reduce_scatter", "INT", ("V", 4, 3, 7), ragged(P), O.SUM, soff=1, roff=3, old=True, seed=25),
+    ], RC.FORM_DIRECT, old=True)
+
+
+TILES_INT = ("V", 409, 4, 6)  # 1636 elements per item
+
+
+def test_direct_form_three_tiles_and_a_partial_one():
+    run_world(3, [
+        Case("allreduce", "INT", TILES_INT, 1, O.SUM, soff=1, roff=1, seed=31),
+        Case("scan", "INT", TILES_INT, 1, O.SUM, soff=1, roff=3, seed=32),
+        Case("reduce_scatter", "INT", ("V", 41, 4, 6), [4, 0, 6], O.SUM, soff=1, roff=1, seed=33),  # 1640 elements
+        Case("allreduce", "DOUBLE", BLOCKS, 90, O.SUM, soff=0, roff=0, seed=34),               # 1620 16-B granules
+        Case("scan", "DOUBLE", BLOCKS, 90, O.MAX, soff=0, roff=2, seed=35),
+        Case("reduce_scatter", "DOUBLE", BLOCKS, [40, 0, 50], O.MIN, soff=0, roff=0, seed=36),
+    ], RC.FORM_DIRECT)
+
+
+# ---- the pack path --------------------------------------------------------------------------------------
+def mixed(r):
+    """12 elements per item on every rank: a Vector on rank 0, an Indexed type elsewhere"""
+    return ("V", 4, 3, 7) if r == 0 else ("I", (5, 7), (9, 0))
+
+
+def pack_cases(P, spec=ODD, ispec=RI):
+    return [
+        Case("allreduce", "INT", spec, 2, O.SUM, soff=1, roff=2, seed=41),
+        Case("reduce", "INT", spec, 2, O.MAX, soff=1, roff=2, root=P - 1, seed=42),
+        Case("scan", "INT", ispec, 2, O.SUM, soff=1, roff=0, seed=43),
+        Case("reduce_scatter", "INT", ispec, ragged(P), O.BAND, soff=1, roff=3, seed=44),
+        Case("allreduce", "DOUBLE", spec, 2, O.SUM, soff=1, inplace=[0], seed=45),
+    ]
+
+
+def test_pack_form_when_the_ranks_layouts_differ():
+    run_world(3, pack_cases(3, mixed, mixed), RC.FORM_PACK)
+
+
+def test_pack_form_at_p9():
+    run_world(9, pack_cases(9), RC.FORM_PACK)
+
+
+def test_pack_form_under_smp_copy():
+    old = os.environ.get("MPJX_SMP_COPY")
+    os.environ["MPJX_SMP_COPY"] = "1"
+    try:
+        run_world(3, pack_cases(3), RC.FORM_PACK)
+    finally:
+        if old is None:
+            del os.environ["MPJX_SMP_COPY"]
+        else:
+            os.environ["MPJX_SMP_COPY"] = old
+
+
+# ---- P = 1, through the C ABI ---------------------------------------------------------------------------
+def p1_call(comm, case, dt, sptr, rptr):
+    h, f = comm.handle, RC.FLAG_BLOCKING
+    if case.kind == "allreduce":
+        _lib.call("mpjx_allreduce_dt", h, sptr, rptr, case.n, dt.code, case.op, f, None)
+    elif case.kind == "reduce":
+        _lib.call("mpjx_reduce_dt", h, sptr, rptr, case.n, dt.code, case.op, 0, f, None)
+    elif case.kind == "scan":
+        _lib.call("mpjx_scan_dt", h, sptr, rptr, case.n, dt.code, case.op, f, None)
+    else:
+        _lib.call("mpjx_reduce_scatter_dt", h, sptr, rptr, (ctypes.c_int64 * 1)(case.n[0]), dt.code, case.op, f, None)
+
+
+P1_CASES = {
+    "vector_x3_at_offset_1": ("INT", ("V", 6, 2, 5), 3, 1, 2, False),
+    "indexed_x4": ("INT", ("I", (2, 1), (9, 4)), 4, 0, 1, False),
+    "in_place": ("INT", ("V", 6, 2, 5), 3, 1, 1, True),
+    "count_0": ("INT", ("V", 6, 2, 5), 0, 1, 2, False),
+    "empty_type": ("INT", ("V", 0, 3, 7), 5, 1, 2, False),
+    "double_blocks": ("DOUBLE", BLOCKS, 2, 0, 2, False),
+}
+
+
+@pytest.mark.parametrize("kind", ["allreduce", "reduce", "scan", "reduce_scatter"])
+@pytest.mark.parametrize("name", list(P1_CASES))
+def test_p1_is_a_move_through_the_layouts(name, kind):
+    base, spec, n, soff, roff, inplace = P1_CASES[name]
+    case = Case(kind, base, spec, [n] if kind == "reduce_scatter" else n, O.SUM, soff=soff, roff=roff,
+                inplace=[0] if inplace else [], seed=51)
+    send, exp, idx = RC.expected(case, 1)[0]
+    f = case.form(0)
+    dt = f.make()
+    comms = mpi.smp_world(1, [0])
+    try:
+        sbuf = torch.from_numpy(send).cuda()
+        rbuf = sbuf if inplace else torch.full((exp.size,), RC.SENT, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        p1_call(comms[0], case, dt, sbuf.data_ptr() + soff * f.bsz, rbuf.data_ptr() + (soff if inplace else roff) * f.bsz)
+        assert RC.last_form(comms[0]) == RC.FORM_MOVE
+        assert RC.differs(case, rbuf.cpu().numpy(), exp, idx, f, name) is None
+        if not inplace:
+            assert SC.differs(sbuf.cpu().numpy(), send, name + " (send buffer)") is None
+    finally:
+        free(comms)
+        dt.Free()
+
+
+def test_a_basic_code_is_the_contiguous_call():
+    comms = mpi.smp_world(1, [0])
+    try:
+        s = torch.arange(64, dtype=torch.int32, device="cuda")
+        r = torch.full((64,), -1, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        _lib.call("mpjx_allreduce_dt", comms[0].handle, s.data_ptr(), r.data_ptr(), 10, MPI.INT.code, O.SUM, RC.FLAG_BLOCKING, None)
+        assert RC.last_form(comms[0]) == RC.FORM_CONTIGUOUS
+        assert r[:10].tolist() == list(range(10)) and bool((r[10:] == -1).all())
+    finally:
+        free(comms)
+
+
+# ---- errors on every rank, with nothing written -----------------------------------------------------------
+def error_world(P, call, faithful=False):
+    """call(comm, sbuf, rbuf) on every rank of a direct-capable world; returns per rank (message, status,
+    receive buffer still the sentinel)."""
+    comms = mpi.smp_world(P, [0] * P, faithful=faithful)
+
+    def body(c):
+        s = torch.arange(256, dtype=torch.int32, device="cuda")
+        r = torch.full((256,), -1, dtype=torch.int32, device="cuda")
+        try:
+            call(c, s, r)
+        except MPIException as e:
+            torch.cuda.synchronize()
+            return str(e), bool((r == -1).all()) and s.tolist() == list(range(256))
+        return None, False
+    try:
+        out, err = run_ranks(comms, body, limit=30)
+        assert not any(err), err
+        return out
+    finally:
+        free(comms)
+
+
+def test_packed_length_mismatch_fails_every_rank():
+    def call(c, s, r):
+        v = Datatype.Vector(3, 2, 5, MPI.INT)
+        try:
+            c.Allreduce(s, 0, r, 0, 2 if c.Rank() == 0 else 3, v, MPI.SUM)
+        finally:
+            v.Free()
+    for msg, untouched in error_world(3, call):
+        assert msg and "(-1)" in msg and "reduces 18 elements but rank 0 reduces 12" in msg, msg
+        assert untouched
+
+
+def test_base_type_mismatch_fails_every_rank():
+    def call(c, s, r):
+        v = Datatype.Vector(3, 2, 5, MPI.INT if c.Rank() == 0 else MPI.FLOAT)
+        try:
+            if c.Rank() == 0:
+                c.Scan(s, 0, r, 0, 2, v, MPI.SUM)
+            else:
+                c.Scan(s.view(torch.float32), 0, r.view(torch.float32), 0, 2, v, MPI.SUM)
+        finally:
+            v.Free()
+    for msg, untouched in error_world(2, call):
+        assert msg and "(-1)" in msg and "base type FLOAT but rank 0 base type INT" in msg, msg
+        assert untouched
+
+
+def test_a_partial_overlap_on_one_rank_fails_every_rank():
+    seen = {}
+
+    def call(c, s, r):
+        v = Datatype.Vector(3, 2, 5, MPI.INT)
+        seen[c.Rank()] = s
+        try:
+            if c.Rank() == 1:  # the receive layout starts one element into the send layout
+                c.Allreduce(s, 0, s, 1, 2, v, MPI.SUM)
+            else:
+                c.Allreduce(s, 0, r, 0, 2, v, MPI.SUM)
+        finally:
+            v.Free()
+    for msg, untouched in error_world(2, call):
+        assert msg and "(-1)" in msg and "rank 1" in msg and "share a byte" in msg, msg
+        assert untouched
+
+
+def test_faithful_is_unsupported_on_every_rank():
+    def call(c, s, r):
+        v = Datatype.Vector(3, 2, 5, MPI.INT)
+        try:
+            c.Allreduce(s, 0, r, 0, 2, v, MPI.SUM)
+        finally:
+            v.Free()
+    for msg, untouched in error_world(2, call, faithful=True):
+        assert msg and "(-6)" in msg and "MPJX_FLAG_FAITHFUL" in msg, msg
+        assert untouched
+
+
+def test_mirror_errors():
+    comms = mpi.smp_world(1, [0])
+    v = Datatype.Vector(3, 2, 5, MPI.INT)
+    try:
+        s = torch.zeros(64, dtype=torch.int32, device="cuda")
+        with pytest.raises(MPIException, match="layout span"):  # 6 items span 72 elements
+            comms[0].Allreduce(s, 0, s, 0, 6, v, MPI.SUM)
+        with pytest.raises(MPIException, match="device-resident"):
+            comms[0].Scan(np.zeros(64, np.int32), 0, np.zeros(64, np.int32), 0, 1, v, MPI.SUM)
+    finally:
+        free(comms)
+        v.Free()
