@@ -468,6 +468,47 @@ int mpjx_scan_dt(mpjx_comm_t comm, const void *sendbuf, void *recvbuf, int64_t c
                  unsigned flags, void *stream);
 int mpjx_comm_last_dt_form(mpjx_comm_t comm, int *form);
 
+/* ---- Pack, Unpack, Pack_size (Comm.Pack / Unpack / Pack_size, src/mpi/Comm.java:1860-1983) ----------------
+ * `count` items of any datatype (basic, pair or derived) to and from ONE section of an mpjbuf static-buffer
+ * image, the form mpjx_mpjbuf_combine, niodev and the Java side read. A section starts at
+ * h = round_up(position, 8) (src/mpjbuf/Buffer.java:609-704, NIOBuffer.java:520-563):
+ *   byte h          the mpjbuf type code = the base type's code - 1
+ *   bytes h+1..h+3  zero
+ *   bytes h+4..h+7  big-endian int32 count of BASE elements (count * the type's size; a pair is 2)
+ *   from h+8        the elements in PACK order (item by item, blocks in the constructor's order), each base
+ *                   word big-endian; a pair type's words are its base type's
+ * *position goes in and comes out as h + 8 + the payload's bytes; it is computed on the host. The reference
+ * writes the count field only at the next putSectionHeader or at commit(); mpjx_pack writes it at once, so
+ * the image after the call is the committed one. Bytes between position and h are left as they were.
+ * count == 0 writes (or expects) a header with count 0.
+ * One kernel does layout, byte swap and header in a single pass (k_pack). Both calls are LOCAL, not
+ * collective: they take the communicator for its stream convention (enqueued on `stream`, ordered after its
+ * previous call, asynchronous like the *_dt calls) and for its cache of the irregular types' device tables.
+ * inbuf / outbuf is the buffer position of item 0; item k lies k extents on and lb is NOT subtracted, as in
+ * mpjx_alltoallv_dt. image is device memory or pinned host memory (mpjx_host_alloc); it must not share bytes
+ * with the buffer.
+ *   MPJX_ERR_ARG, before anything is launched: an unknown or freed type; a NULL position, image or (unpack)
+ *   status; a NULL inbuf / outbuf with a nonzero count; a negative count or position; count * size above
+ *   2^31 - 1 (the header field is a Java int); inbuf / outbuf not aligned to the base element (a Java array
+ *   always is); image not 8-byte aligned; a section that would end past image_bytes (mpjx_pack checks what it
+ *   really needs, not mpjx_pack_size); for mpjx_unpack a type whose own blocks share a byte; memory that is
+ *   not GPU-accessible. These are checked before the communicator is looked at.
+ * mpjx_unpack reads exactly one section at round_up(*position, 8) into `count` items. The kernel reads the
+ * header itself (the image may have arrived in device memory) before any payload byte: a wrong type code
+ * (MPJX_MPJBUF_BAD_TYPE), a count whose payload passes image_bytes (MPJX_MPJBUF_OVERRUN) or a count that is
+ * not count * size (MPJX_MPJBUF_BAD_COUNT) leave outbuf untouched and store that code into *status, a
+ * device-accessible int the caller zeroes (the contract of mpjx_mpjbuf_combine); *position still advances by
+ * the expected section. Bytes of outbuf between the type's blocks keep their contents.
+ * mpjx_pack_size returns the reference's value, padding quirk included: t = 8 + count * size in bytes,
+ * *bytes = t + t % 8 (src/mpi/BasicType.java:209-220). It is an upper bound of what mpjx_pack writes only for
+ * a section that starts at a multiple of 8: from position 1, INT x 2 occupies bytes 8..23 of the image, while
+ * 1 + mpjx_pack_size = 17. */
+int mpjx_pack_size(int64_t count, int type, int64_t *bytes);
+int mpjx_pack(mpjx_comm_t comm, const void *inbuf, int64_t count, int type, void *image, int64_t image_bytes,
+              int64_t *position, void *stream);
+int mpjx_unpack(mpjx_comm_t comm, const void *image, int64_t image_bytes, int64_t *position, void *outbuf,
+                int64_t count, int type, int *status, void *stream);
+
 /* ---- host-resident variants (Java heap arrays / mpjbuf payloads) ---------------------------------
  * Synchronous. Buffers are ordinary host memory; the library stages them through device memory.
  * These are what the JNI shim calls with GetPrimitiveArrayCritical / GetDirectBufferAddress

@@ -12,6 +12,8 @@
 //   on either side (or two different types of one base type) the nine data-movement calls build the tables of
 //   mpjx_alltoallv_dt: counts in items, v-call displacements in base elements, block j of an equal-count
 //   call j * count extents into the buffer (mpjx.h)
+//   ::Pack_size / ::Pack / ::Unpack          src/mpi/Comm.java:1860-1983: one mpjbuf section from, or into, items
+//   of any datatype on a device buffer; the mpjbuf.Buffer is a pointer and a size (device or pinned host memory)
 //   mpi::MPIException                       src/mpi/MPIException.java:42 (unchecked, like the Java one)
 //   mpi::MPI::isOldSelected                  conf mpjexpress.mpi.old.collectives (src/mpi/MPI.java:70,266)
 // Buffers are typed pointers; offsets and counts are in elements. Device pointers take the device
@@ -344,6 +346,39 @@ class Intracomm {
                          sendtype.code, nullptr),
           "Alltoallv");
     sync();
+  }
+
+  // ---- Pack / Unpack / Pack_size (src/mpi/Comm.java:1860-1983): one mpjbuf section from, or into, items of
+  // any datatype on a device buffer. The image (mpjbuf.Buffer there) is `bytes` bytes of device or pinned host
+  // memory; positions are bytes; the new position is returned. Local calls (mpjx.h) ----
+  int64_t Pack_size(int incount, const Datatype& dt) const {
+    int64_t n = 0;
+    check(mpjx_pack_size(incount, dt.code, &n), "Pack_size");
+    return n;
+  }
+  template <class T>
+  int64_t Pack(const T* inbuf, int offset, int incount, const Datatype& dt, void* outbuf, int64_t bytes,
+               int64_t position) {
+    size_ok<T>(dt);
+    check(mpjx_pack(c_, inbuf + offset, incount, dt.code, outbuf, bytes, &position, nullptr), "Pack");
+    sync();
+    return position;
+  }
+  // a section of another type or count, or one that passes the end of the image, throws and leaves outbuf untouched
+  template <class T>
+  int64_t Unpack(const void* inbuf, int64_t bytes, int64_t position, T* outbuf, int offset, int outcount,
+                 const Datatype& dt) {
+    size_ok<T>(dt);
+    void* st = nullptr;  // the kernel's status word: pinned, so the host reads it after the call
+    check(mpjx_host_alloc(&st, sizeof(int)), "Unpack");
+    *(volatile int*)st = 0;
+    int rc = mpjx_unpack(c_, inbuf, bytes, &position, outbuf + offset, outcount, dt.code, (int*)st, nullptr);
+    if (rc == MPJX_SUCCESS) rc = mpjx_comm_synchronize(c_);
+    const int code = *(volatile int*)st;
+    (void)mpjx_host_free(st);
+    check(rc, "Unpack");
+    if (code) throw MPIException("Unpack: malformed section (status " + std::to_string(code) + ")");
+    return position;
   }
 
   // ---- host-resident arrays (the Java heap array case) ----

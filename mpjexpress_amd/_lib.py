@@ -88,6 +88,9 @@ def _declare(L):
         "mpjx_reduce_scatter_dt": ([vp, vp, vp, pi64, c_int, c_int, c_uint, vp], c_int),
         "mpjx_scan_dt": ([vp, vp, vp, c_i64, c_int, c_int, c_uint, vp], c_int),
         "mpjx_comm_last_dt_form": ([vp, ctypes.POINTER(c_int)], c_int),
+        "mpjx_pack_size": ([c_i64, c_int, pi64], c_int),
+        "mpjx_pack": ([vp, vp, c_i64, c_int, vp, c_i64, pi64, vp], c_int),
+        "mpjx_unpack": ([vp, vp, c_i64, pi64, vp, c_i64, c_int, vp, vp], c_int),
         "mpjx_reduce_host": ([vp, vp, vp, c_i64, c_int, c_int, c_int, c_uint], c_int),
         "mpjx_allreduce_host": ([vp, vp, vp, c_i64, c_int, c_int, c_uint], c_int),
         "mpjx_reduce_scatter_host": ([vp, vp, vp, pi64, c_int, c_int, c_uint], c_int),

@@ -1956,6 +1956,76 @@ static int alltoallv_dt_entry(mpjx_comm_t c, const void* sendbuf, const int64_t*
   return dt_run(c, p, stream);
 }
 
+// ---- mpjx_pack / mpjx_unpack / mpjx_pack_size (Comm.Pack, Unpack, Pack_size: src/mpi/Comm.java:1860-1983) ----
+// One mpjbuf section from, or into, `count` items of any datatype: the section arithmetic and the descriptor
+// are mpjx_pack_plan.hpp's, the kernel k_pack (mpjx_k_pack.hip: layout, byte swap and header in one pass).
+// Local calls: no rank waits for another, and a rejected call does not fail the world. Every argument is
+// checked before the communicator is touched, so the checks need no device.
+static int pack_entry(mpjx_comm_t c, bool unpack, const void* buf, int64_t count, int type, const void* image,
+                      int64_t image_bytes, int64_t* position, int* status, void* stream) {
+  const char* who = unpack ? "mpjx_unpack" : "mpjx_pack";
+  TypeForm f;
+  if (!type_form(type, &f)) return fail(MPJX_ERR_ARG, "%s: unknown or freed datatype code %d", who, type);
+  if (!position) return fail(MPJX_ERR_ARG, "%s: position is NULL", who);
+  PackSection sec;
+  std::string err;
+  if (!plan_pack_section(*position, count, f.size(), f.bsz, image_bytes, &sec, &err))
+    return fail(MPJX_ERR_ARG, "%s: %s", who, err.c_str());
+  if (!image) return fail(MPJX_ERR_ARG, "%s: image is NULL", who);
+  if (unpack && !status) return fail(MPJX_ERR_ARG, "%s: status is NULL", who);
+  if (sec.words > 0 && !buf)
+    return fail(MPJX_ERR_ARG, "%s: NULL %s with count %lld", who, unpack ? "outbuf" : "inbuf", (long long)count);
+  if (sec.words > 0 && (uintptr_t)buf % (uintptr_t)f.bsz)
+    return fail(MPJX_ERR_ARG, "%s: %s %p is not aligned to the %d-byte base element", who, unpack ? "outbuf" : "inbuf",
+                buf, f.bsz);
+  if ((uintptr_t)image % 8)
+    return fail(MPJX_ERR_ARG, "%s: image %p is not 8-byte aligned (the mpjbuf ALIGNMENT_UNIT)", who, image);
+  if (unpack && f.irr && f.irr->self_overlap)
+    return fail(MPJX_ERR_ARG, "%s: datatype %d has blocks that share a byte: it can be packed, not unpacked into", who,
+                type);
+  SideBytes lay;
+  if (!plan_side(f, (uint64_t)(uintptr_t)buf, count, 0, &lay, &err)) return fail(MPJX_ERR_ARG, "%s: %s", who, err.c_str());
+  if (!c) return fail(MPJX_ERR_ARG, "%s: comm is NULL", who);
+  if (sec.words > 0) CHK(check_dev_ptr(buf, unpack ? "outbuf" : "inbuf"));
+  CHK(check_dev_ptr(image, "image"));
+  if (unpack) CHK(check_dev_ptr(status, "status"));
+  Call k;
+  CHK(k.begin(c, stream, f.base));
+  const IdxEnt* tab = nullptr;
+  if (sec.words > 0) CHK(idx_table(c, lay, k.s, &tab));
+  PackSeg sg;
+  plan_pack_seg(lay, tab, (uint64_t)(uintptr_t)image, image_bytes, sec, f.base, f.bsz, status, &sg);
+  const hipError_t e = launch_pack(sg, unpack, k.s);
+  if (e == hipErrorNoBinaryForGpu || e == hipErrorInvalidDeviceFunction)
+    return fail(MPJX_ERR_NO_DEVICE, "no gfx950 kernel image for this device: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return fail(MPJX_ERR_HIP, "%s launch: %s", who, hipGetErrorString(e));
+  *position = sec.end;
+  return k.end();
+}
+
+extern "C" int mpjx_pack_size(int64_t count, int type, int64_t* bytes) {
+  TypeForm f;
+  if (!type_form(type, &f)) return fail(MPJX_ERR_ARG, "mpjx_pack_size: unknown or freed datatype code %d", type);
+  if (!bytes) return fail(MPJX_ERR_ARG, "mpjx_pack_size: bytes is NULL");
+  if (count < 0) return fail(MPJX_ERR_ARG, "mpjx_pack_size: negative count %lld", (long long)count);
+  const int64_t item = f.size() * f.bsz;  // <= 2^62 (the type constructors)
+  if (item > 0 && count > (kMoveMaxBytes - 16) / item)
+    return fail(MPJX_ERR_ARG, "mpjx_pack_size: %lld items of %lld bytes reach beyond 2^62 bytes", (long long)count,
+                (long long)item);
+  *bytes = pack_size_bytes(count, item);
+  return MPJX_SUCCESS;
+}
+
+extern "C" int mpjx_pack(mpjx_comm_t c, const void* inbuf, int64_t count, int type, void* image, int64_t image_bytes,
+                         int64_t* position, void* stream) {
+  return pack_entry(c, false, inbuf, count, type, image, image_bytes, position, nullptr, stream);
+}
+
+extern "C" int mpjx_unpack(mpjx_comm_t c, const void* image, int64_t image_bytes, int64_t* position, void* outbuf,
+                           int64_t count, int type, int* status, void* stream) {
+  return pack_entry(c, true, outbuf, count, type, image, image_bytes, position, status, stream);
+}
+
 static int allgather_entry(mpjx_comm_t c, const void* sendbuf, void* recvbuf, int64_t count, int type, void* stream) {
   int esz;
   CHK(moves_begin(c, type, &esz));

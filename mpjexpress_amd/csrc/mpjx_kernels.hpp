@@ -31,6 +31,7 @@
 #include "mpjx_moves_plan.hpp"
 #include "mpjx_ops.hpp"
 #include "mpjx_indexed_plan.hpp"
+#include "mpjx_pack_plan.hpp"
 #include "mpjx_strided_plan.hpp"
 
 namespace mpjx {
@@ -653,6 +654,10 @@ hipError_t launch_strided(const std::vector<StridedSeg>& segs, hipStream_t s);
 // The same for moves with an irregular layout on either side (mpjx_k_indexed.hip): segments planned by
 // plan_indexed_seg, their device tables uploaded on `s` or earlier; kIndexedMax segments per launch.
 hipError_t launch_indexed(const std::vector<IndexedSeg>& segs, hipStream_t s);
+
+// One mpjbuf section packed from (unpack: unpacked into) a buffer of any layout (mpjx_k_pack.hip): the descriptor
+// planned by plan_pack_seg, an irregular layout's device table uploaded on `s` or earlier. One launch.
+hipError_t launch_pack(const PackSeg& seg, bool unpack, hipStream_t s);
 
 // IPC device sync (mpjx_ipc.hip): flag slots of the peers (peer[j] = peer j's slot for this rank),
 // this rank's own slots, and the bounded wait's limits; counter = a zeroed device word for the

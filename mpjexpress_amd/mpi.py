@@ -13,6 +13,9 @@ reference's own programs (e.g. test/mpi/ccl/allreduce.java):
     comm.Allgather / Allgatherv / Gatherv / Scatterv / Alltoall / Alltoallv(sendbuf, sendoffset, sendcount[s],
         [sdispls,] sendtype, recvbuf, recvoffset, recvcount[s], [rdispls,] recvtype[, root])
                                                  src/mpi/Intracomm.java:363-690 (device tensors only)
+    comm.Pack_size(incount, datatype), comm.Pack(inbuf, offset, incount, datatype, outbuf, position),
+    comm.Unpack(inbuf, position, outbuf, offset, outcount, datatype)     src/mpi/Comm.java:1860-1983
+        (one mpjbuf section; the mpjbuf.Buffer is a torch.uint8 image on the device or in pinned memory)
 
 Buffers are device-resident torch tensors (the device path) or numpy arrays (the host-resident
 path, as Java heap arrays are). Offsets and counts are in elements. Calls block until the result is
@@ -624,6 +627,57 @@ class Intracomm:
         rp = _dev_ptr(recvbuf, recvoffset, recvtype, rspan)
         _wrap("mpjx_alltoallv", self._h, sp, sc, sd, rp, rc, rd, sendtype.code, None)
         self._sync_out()
+
+    # -- Pack / Unpack / Pack_size (src/mpi/Comm.java:1860-1983): one mpjbuf section from, or into, items of any
+    # datatype on a device tensor. The image (mpjbuf.Buffer there) is a torch.uint8 tensor on the device or in
+    # pinned host memory; positions are bytes. Local calls (include/mpjx.h).
+    def Pack_size(self, incount, datatype):
+        n = ctypes.c_int64()
+        _wrap("mpjx_pack_size", incount, datatype.code, ctypes.byref(n))
+        return n.value
+
+    def _image(self, name, img):
+        torch = _lib.torch
+        if not _is_torch(img) or img.dtype != torch.uint8 or not img.is_contiguous():
+            raise MPIException(f"{name}: the image must be a contiguous torch.uint8 tensor")
+        if not (img.is_cuda or img.is_pinned()):
+            raise MPIException(f"{name}: the image must be on the device or in pinned host memory")
+        return img.data_ptr(), img.numel()
+
+    def Pack(self, inbuf, offset, incount, datatype, outbuf, position):
+        """Packs incount items of datatype from inbuf (base element `offset` on) into the image outbuf as one
+        section at round_up(position, 8); returns the new position."""
+        if not _is_torch(inbuf):
+            raise MPIException("Pack is provided for device-resident buffers")
+        ip, nb = self._image("Pack", outbuf)
+        self._sync_in(inbuf, outbuf)
+        p = _dev_ptr_dt(inbuf, offset, datatype, incount)
+        pos = ctypes.c_int64(position)
+        _wrap("mpjx_pack", self._h, p, incount, datatype.code, ip, nb, ctypes.byref(pos), None)
+        self._sync_out()
+        return pos.value
+
+    def Unpack(self, inbuf, position, outbuf, offset, outcount, datatype):
+        """Unpacks the section at round_up(position, 8) of the image inbuf into outcount items of datatype in
+        outbuf (base element `offset` on); returns the new position. A section of another type or count, or one
+        that passes the end of the image, raises MPIException and leaves outbuf untouched."""
+        if not _is_torch(outbuf):
+            raise MPIException("Unpack is provided for device-resident buffers")
+        ip, nb = self._image("Unpack", inbuf)
+        self._sync_in(inbuf, outbuf)
+        p = _dev_ptr_dt(outbuf, offset, datatype, outcount)
+        torch = _lib.torch
+        status = torch.zeros(1, dtype=torch.int32, device=torch.device("cuda", self.device))
+        torch.cuda.synchronize(self.device)
+        pos = ctypes.c_int64(position)
+        _wrap("mpjx_unpack", self._h, ip, nb, ctypes.byref(pos), p, outcount, datatype.code, status.data_ptr(), None)
+        self._sync_out()
+        code = int(status.item())
+        if code:
+            what = {1: "the section holds another type", 2: "the section's count is not outcount * Size()",
+                    3: "the section passes the end of the image"}.get(code, "malformed section")
+            raise MPIException(f"Unpack: {what} (status {code}) at position {position}")
+        return pos.value
 
     def Bcast(self, buf, offset, count, datatype, root):
         if not _is_torch(buf):
