@@ -2,7 +2,8 @@
 // no HIP (tests/test_reduce_dt_abi.py builds it under -fsanitize=address,undefined). It walks the functions
 // k_pway_dt calls (mpjexpress_amd/csrc/mpjx_reduce_dt_plan.hpp) against a block list expanded here:
 //   - the byte offset of EVERY granule of a layout, in the element form and in the 16-B form;
-//   - the choice between the two over the layout and the P send + Q receive pointers;
+//   - the choice between the two over the layout and the P send + Q receive pointers, and over the layouts and
+//     pointer residues of the GPU instantiation matrix;
 //   - Reduce_scatter's ranges and the rebasing of the receiving rank's pointer;
 //   - same_form on types built twice, and on types that differ.
 #include <stdio.h>
@@ -143,6 +144,43 @@ static void granule() {
   CHECK(reduce_dt_granule_log(lay, 4, ok, 6) == 2);
 }
 
+// The layouts and pointer residues of tests/test_gpu_reduce_dt_matrix.py (reduce_dt_cases.matrix_spec and
+// matrix_widths), which cannot observe the width a call took: Vector(3, 32 B, 48 B) of every type takes the 16-B
+// form where all P send and Q receive pointers are multiples of 16, and the element form with the send pointers
+// one base element and the receive pointers two base elements further — but for the 16-B pairs, whose element is
+// the 16-B granule at any address.
+static void matrix_layouts() {
+  const struct { int code, elem; } types[13] = {{1, 1}, {2, 2}, {3, 2}, {4, 1}, {5, 4}, {6, 8}, {7, 4}, {8, 8},
+                                                {0x103, 4}, {0x105, 8}, {0x106, 16}, {0x107, 8}, {0x108, 16}};
+  for (const auto& t : types) {
+    const TypeForm old = basic(t.code);
+    const TypeForm f = vec(3, 32 / t.elem, 48 / t.elem, old);
+    CHECK(reduce_dt_elem_bytes(f) == t.elem);
+    CHECK(f.size() * f.bsz == 96 && f.extent() * f.bsz == 128);
+    uint32_t elog = 0;
+    while ((1 << elog) < t.elem) elog++;
+    for (int64_t items : {3, 43, 171}) {
+      SideBytes lay;
+      std::string err;
+      CHECK(reduce_dt_layout(f, items, &lay, &err));
+      CHECK(lay.total() == 96 * items);
+      for (int P = 2; P <= 8; P++) {
+        uint64_t at0[16], at12[16];  // P send pointers, then P receive pointers
+        for (int i = 0; i < 2 * P; i++) {
+          at0[i] = 0x7f0000001000ull + 0x4000ull * (uint64_t)i;
+          at12[i] = at0[i] + (uint64_t)((i < P ? 1 : 2) * f.bsz);
+        }
+        CHECK(reduce_dt_granule_log(lay, t.elem, at0, 2 * P) == 4);
+        CHECK(reduce_dt_granule_log(lay, t.elem, at0, P + 1) == 4);  // Reduce: the root's receive pointer only
+        CHECK(reduce_dt_granule_log(lay, t.elem, at12, 2 * P) == elog);
+        CHECK(reduce_dt_granule_log(lay, t.elem, at12, P + 1) == elog);
+      }
+      walk(f, items, 4, "the matrix layout, 16 B");
+      walk(f, items, elog, "the matrix layout, elements");
+    }
+  }
+}
+
 // Block r of Reduce_scatter: granule i of its range, read at the rebased pointer, is granule i of a layout of
 // recvcounts[r] items at the receive buffer's own origin
 static void ranges(const TypeForm& f, uint32_t glog, const char* what) {
@@ -191,6 +229,7 @@ static void forms() {
 int main() {
   offsets();
   granule();
+  matrix_layouts();
   forms();
   ranges(vec(4, 3, 7, basic(5)), 2, "Vector(4,3,7) INT");
   ranges(vec(9, 4, 10, basic(8)), 4, "Vector(9,4,10) DOUBLE 16 B");

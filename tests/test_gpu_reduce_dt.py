@@ -1,9 +1,11 @@
 """GPU: Reduce, Allreduce, Reduce_scatter and Scan on derived datatypes, in-process on device 0: the one-rank
 move through the C ABI, the layout-direct kernel k_pway_dt in one-device multicore worlds of 2, 3, 5 and 8 rank
-threads, the pack path (ranks whose layouts differ, P = 9, MPJX_SMP_COPY=1) and the errors every rank must
-return before anything moves. Every case asserts the form the call took (mpjx_comm_last_dt_form), so the pack
-path cannot stand in for a broken kernel. The expectation is tests/reduce_dt_cases.py's: the oracle on the
-packed vectors, scattered into a sentinel-filled buffer that is compared whole.
+threads, the operand order and root of every host-built operand list in worlds of 2 to 8 (test_order_and_root),
+the pack path (ranks whose layouts differ, P = 9, MPJX_SMP_COPY=1) and the errors every rank must return before
+anything moves. Every (functor, kind, P, width) of the kernel is launched by tests/test_gpu_reduce_dt_matrix.py.
+Every case asserts the form the call took (mpjx_comm_last_dt_form), so the pack path cannot stand in for a broken
+kernel. The expectation is tests/reduce_dt_cases.py's: the oracle on the packed vectors, scattered into a
+sentinel-filled buffer that is compared whole.
 
 The kernel's tile is 256 lanes x Unroll<P> granules (4 at P = 2, 2 at P = 3 and 4, 1 above; one granule per
 lane for 8- and 16-bit types in the 16-B form at P >= 3): at P = 3 that is 512 granules, so the TILES cases
@@ -139,6 +141,19 @@ def test_direct_form_three_tiles_and_a_partial_one():
         Case("scan", "DOUBLE", BLOCKS, 90, O.MAX, soff=0, roff=2, seed=35),
         Case("reduce_scatter", "DOUBLE", BLOCKS, [40, 0, 50], O.MIN, soff=0, roff=0, seed=36),
     ], RC.FORM_DIRECT)
+
+
+# ---- operand order and root ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("row,P", RC.ORDER_ROWS, ids=[f"{row}-P{P}" for row, P in RC.ORDER_ROWS])
+def test_order_and_root(row, P):
+    """reduce_dt_cases.order_group: ops and inputs whose result shows a wrong operand list, root or algorithm
+    (tests/test_reduce_dt_case_power.py holds that they do), each on a 16-B-form and an element-form layout:
+    Reduce at every root (K_MST's root, rd_mst's swapped list at P = 2), FT Reduce at roots 0 and P - 1, ragged
+    Reduce_scatter with a zero (the P = 2 ring on FLOAT, MST on the pair type; FT under the old collectives),
+    Scan, and the old collectives' Allreduce (every rank's own FT order, through the temporaries when a rank is
+    in place)."""
+    cases = RC.order_group(row, P)
+    run_world(P, cases, RC.FORM_DIRECT, old=cases[0].old)
 
 
 # ---- the pack path --------------------------------------------------------------------------------------
