@@ -7,7 +7,11 @@
 //   - the granule: an 8-aligned payload against a 16-aligned one, never below the base word
 //   - for EVERY granule of a set of layouts (contiguous, Vector, Indexed with lb > 0, 600 reversed blocks) the
 //     kernel's buffer-side address against SideBytes::at, and the payload side linear
+// With --cases it plans the cases given on stdin instead and prints each one's cell (run_cases below;
+// tests/test_pack_cases.py feeds it tests/pack_cases.py).
 #include <stdio.h>
+
+#include <iostream>
 
 #include "../../mpjexpress_amd/csrc/mpjx_pack_plan.hpp"
 
@@ -187,7 +191,52 @@ static void test_addresses() {
   walk(rev, 0x10000, 2, 0);
 }
 
-int main() {
+// --cases: one case of tests/pack_cases.py per line of stdin,
+//   <base code> B 0 | V 3 <count> <blocklength> <stride> | I 2n <n blocklengths> <n displacements>
+//   <count> <buffer offset in base elements> <position>
+// planned over a 16-byte aligned buffer and image. Prints per case
+//   glog wlog lin tab nb ngran lo hi
+// (tab: the layout has a block table; nb: its blocks; lo, hi: the bytes of the buffer the layout touches, from the
+// buffer's start). A case of up to 4096 granules has every granule's address walked as above.
+static int run_cases() {
+  const uint64_t buf = 0x10000000, img = 0x40000000;
+  long long code, k, v;
+  char ctor;
+  int n = 0;
+  while (std::cin >> code >> ctor >> k) {
+    V a;
+    for (long long i = 0; i < k + 3 && (std::cin >> v); i++) a.push_back(v);
+    if ((long long)a.size() != k + 3 || k < 0 || (ctor == 'B' && k != 0) || (ctor == 'V' && k != 3) ||
+        (ctor == 'I' && (k % 2 || k == 0)) || (ctor != 'B' && ctor != 'V' && ctor != 'I')) {
+      printf("case %d: malformed\n", n);
+      return 2;
+    }
+    const TypeForm b = basic((int)code);
+    const size_t h = (size_t)k / 2;
+    const TypeForm f = ctor == 'B'   ? b
+                       : ctor == 'V' ? vec(a[0], a[1], a[2], b)
+                                     : indexed(V(a.begin(), a.begin() + (long)h), V(a.begin() + (long)h, a.begin() + (long)k), b);
+    const int64_t count = a[(size_t)k], off = a[(size_t)k + 1], pos = a[(size_t)k + 2];
+    const uint64_t at = buf + (uint64_t)(off * f.bsz);
+    SideBytes lay;
+    const PackSeg sg = seg(f, at, count, img, pos, &lay);
+    uint64_t lo, hi;
+    lay.span(&lo, &hi);
+    if (sg.ngran <= 4096) walk(f, at, count, pos);
+    printf("%u %u %u %d %u %u %lld %lld\n", sg.glog, sg.wlog, sg.lin, sg.lay.tab ? 1 : 0, sg.lay.r.nb.d, sg.ngran,
+           (long long)(lo - buf), (long long)(hi - buf));
+    n++;
+  }
+  if (failures) {
+    printf("pack_plan_test: %d failure(s)\n", failures);
+    return 1;
+  }
+  printf("pack_plan_test: ok (%d cases)\n", n);
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1 && std::string(argv[1]) == "--cases") return run_cases();
   test_section();
   test_pack_size();
   test_header();
