@@ -69,6 +69,11 @@ enum {
   MPJX_SHORT2 = 0x103, MPJX_INT2 = 0x105, MPJX_LONG2 = 0x106, MPJX_FLOAT2 = 0x107, MPJX_DOUBLE2 = 0x108
 };
 
+/* The bound markers MPI.LB / MPI.UB (src/mpi/Datatype.java:68-69; BasicType.java:145-170): no base type, size
+ * 0, lb = ub = 0 with lbSet (LB) or ubSet (UB). Valid only as a component of mpjx_type_struct; every other entry
+ * point returns MPJX_ERR_ARG for them (an unknown datatype code). */
+enum { MPJX_LB = 10, MPJX_UB = 11 };
+
 /* mpi.Op.opCode values (src/mpjdev/Constants.java:53-64; MPI.MAX..MPI.MINLOC at src/mpi/MPI.java:117-130) */
 enum {
   MPJX_MAX = 1, MPJX_MIN = 2, MPJX_SUM = 3, MPJX_PROD = 4, MPJX_LAND = 5,
@@ -344,7 +349,10 @@ int mpjx_alltoallv(mpjx_comm_t comm, const void *sendbuf, const int64_t *sendcou
  *   MPJX_ERR_ARG: a negative count or blocklength, an unknown or freed oldtype, sizes beyond 2^62 bytes.
  *   MPJX_ERR_UNSUPPORTED (the message names what was passed): a stride smaller than the block length
  *   (negative, zero or overlapping), a strided oldtype (Vector of Vector, Contiguous of Vector).
- * Struct and the LB/UB markers are not provided (their sticky bounds are a separate piece of semantics).
+ * An oldtype with explicit bounds (made by mpjx_type_struct with a marker, below) is accepted by both: its items
+ * lie one explicit extent apart, the bounds follow Contiguous.java:71-98 (extent = count*old.extent, lb = old.lb,
+ * ub = lb + extent) and Vector.java:99-135, the sticky flags are handed on, and the blocks are flattened through
+ * the planner of the irregular types below; the result is regular again where its blocks are.
  * Derived codes are handles >= 0x10000 from a process-wide, thread-safe registry, local to the rank as MPI
  * types are (only the signatures must match between ranks). A freed code is never reissued; a freed or
  * unknown code is MPJX_ERR_ARG in every later call. mpjx_type_size() returns 0 for a derived code, so every
@@ -379,7 +387,8 @@ int mpjx_type_info(int type, int *base, int64_t *size, int64_t *extent);
  *   MPJX_ERR_UNSUPPORTED (the message names what was passed): a negative displacement (lb < 0), an Hvector
  *   stride < 1 with count > 1, more than 1,048,576 blocks after merging (a type's device table is 16 B per
  *   block).
- * mpjx_type_layout: lb and ub in elements of the basic type (0 and the extent for every regular type), the
+ * mpjx_type_layout: lb and ub in elements of the basic type (0 and the extent for every regular type without
+ * explicit bounds; the explicit ones for a type made with the markers of mpjx_type_struct, below), the
  * merged block count, and regular = 1 if the type takes the block-move or strided kernel, 0 if the indexed
  * one. mpjx_type_info, mpjx_type_free and mpjx_alltoallv_dt take the new codes like the others; a call
  * enqueued before mpjx_type_free completes with the layout it was given. */
@@ -387,6 +396,47 @@ int mpjx_type_hvector(int64_t count, int64_t blocklength, int64_t stride, int ol
 int mpjx_type_indexed(int n, const int64_t *blocklengths, const int64_t *displacements, int oldtype, int *newtype);
 int mpjx_type_hindexed(int n, const int64_t *blocklengths, const int64_t *displacements, int oldtype, int *newtype);
 int mpjx_type_layout(int type, int64_t *lb, int64_t *ub, int64_t *nblocks, int *regular);
+/* ---- Struct and the LB / UB markers (src/mpi/Struct.java) --------------------------------------------------
+ * Struct(bl[], disp[], types[]): block i is bl[i] items of types[i], one extent of that type apart, starting
+ * disp[i] elements of the BASIC type from the origin; the blocks are packed in the order of the arrays
+ * (StructPacker.pack, Struct.java:448-464). types[i] is any live type or a marker, MPJX_LB / MPJX_UB. All
+ * components that are not markers must have one basic type, which makes a Struct one mpjbuf section like every
+ * other type. The blocks are flattened, merged, stripped of empty ones and normalised as for Indexed: a Struct
+ * whose data blocks are regular IS the Vector of that shape (regular = 1) and takes its path.
+ * Bounds: Struct.computeBounds (Struct.java:149-386) AS WRITTEN, in the order of the arrays, which is NOT
+ * MPI's "markers are sticky minima and maxima":
+ *   - a component with ubSet (an UB marker, or a type made from one) REPLACES ub with
+ *     disp + (bl-1)*extent + its ub: the `if (max_ub > ub)` test is commented out (Struct.java:242-244), so a
+ *     later marker replaces an earlier one, higher or lower;
+ *   - a component without ubSet moves ub to max(its end, disp) whenever its end reaches past every earlier
+ *     such component's (trueUb, Struct.java:251-258), even after a marker: a data block after a marker can
+ *     move ub again;
+ *   - lb mirrors both rules (Struct.java:272-303);
+ *   - a marker is itself a component without the flag for the OTHER bound (an LB at 10 before any data sets ub
+ *     to 10), and components of length 0 take no part.
+ * extent = ub - lb; lbSet / ubSet are sticky: every constructor hands them on with the bounds its own class
+ * computes (Contiguous, Vector, Hvector, Indexed, Hindexed: the minimum and maximum over the blocks of
+ * start + old.lb and start + (bl-1)*old.extent + old.ub). mpiJava 1.2 has no Type_create_resized: a Struct with
+ * an UB marker is how a type is resized, e.g. a column of a row-major matrix to an extent of one element, so
+ * that `count` items are `count` adjacent columns.
+ * Item k of a message starts k*extent after the origin and lb is NOT subtracted (GenericPacker). Extent 0 with
+ * data is legal: every item lies at the same place, which can be sent; receiving more than one such item is
+ * MPJX_ERR_ARG by the self-overlap rule. The blocks of an item may reach past the next item's origin; whether
+ * two items of a receive layout share a byte is part of the exact overlap check of mpjx_alltoallv_dt.
+ * mpjx_type_info and mpjx_type_layout report these bounds (extent = ub - lb); the layout a call touches is
+ * always the blocks' own.
+ *   MPJX_ERR_ARG: n < 0, NULL arrays with n > 0, a negative block length, an unknown or freed component type,
+ *   components of different basic types ("Base types of all component types in a Struct must agree"), sizes
+ *   beyond 2^62 bytes.
+ *   MPJX_ERR_UNSUPPORTED (the message names the value): DATA at a negative displacement (a marker at one is
+ *   fine: lb < 0), an explicit extent below 0 (ub < lb), more than 1,048,576 blocks after merging. */
+int mpjx_type_struct(int n, const int64_t *blocklengths, const int64_t *displacements, const int *types,
+                     int *newtype);
+/* The blocks' own bounds, in elements of the basic type from the item's origin: the lowest element an item
+ * touches and one past the highest (both 0 for an empty type). They equal lb and ub unless the type carries
+ * explicit bounds; `count` items touch [true_lb, (count-1)*extent + true_ub), which is what a buffer must hold.
+ *   MPJX_ERR_ARG: an unknown or freed type, a marker. */
+int mpjx_type_true_bounds(int type, int64_t *true_lb, int64_t *true_ub);
 /* The general block move: sendcounts[j] items of sendtype, the first at sendbuf + sdispls[j], go to rank j;
  * recvcounts[i] items of recvtype from rank i land from recvbuf + rdispls[i]. Every block move and every
  * rooted call is a special case, with zero counts where a rank has nothing to send or receive.
@@ -406,7 +456,11 @@ int mpjx_type_layout(int type, int64_t *lb, int64_t *ub, int64_t *nblocks, int *
  *   both layouts' block bytes, strides, extents and addresses; for an irregular type, every block offset and length).
  * No flags and no faithful mode. Enqueued on `stream`, ordered and failure-marked like the other collectives.
  * A segment whose two layouts are contiguous runs the block-move kernel, one whose two layouts are regular the
- * strided kernel, every other one the indexed kernel (a binary search of the type's block table per granule; the
+ * strided kernel — or, where one layout is a contiguous run and the other has one granule (1, 2, 4, 8 or 16
+ * bytes) per block, consecutive items on consecutive granules, two or more blocks and two or more items (the
+ * element transpose: columns resized to one element), the transpose kernel, which moves tiles through LDS so
+ * that both sides are read and written in consecutive granules; MPJX_TRANSPOSE=0 in the environment, read per
+ * call, keeps the strided kernel for these — every other one the indexed kernel (a binary search of the type's block table per granule; the
  * table is uploaded once per communicator and type, on the stream of the first call that uses it).
  * One rank, and multicore ranks sharing one device (MPJX_SMP_COPY unset): one launch per kernel for the whole
  * world; a base-type or packed-length mismatch between a sender and its receiver is MPJX_ERR_ARG on every
@@ -467,6 +521,15 @@ int mpjx_reduce_scatter_dt(mpjx_comm_t comm, const void *sendbuf, void *recvbuf,
 int mpjx_scan_dt(mpjx_comm_t comm, const void *sendbuf, void *recvbuf, int64_t count, int type, int op,
                  unsigned flags, void *stream);
 int mpjx_comm_last_dt_form(mpjx_comm_t comm, int *form);
+/* The kernels this rank's last data-movement call launched (the nine block moves; the P = 1 and pack forms of
+ * the *_dt reductions set it too), one bit each; 0 on a rank that launched nothing — in a multicore world on
+ * one device rank 0 launches for the world. No reference counterpart, tests read it.
+ *   MPJX_ERR_ARG: comm or mask is NULL. */
+#define MPJX_MOVE_KERNEL_MOVES 1u
+#define MPJX_MOVE_KERNEL_STRIDED 2u
+#define MPJX_MOVE_KERNEL_INDEXED 4u
+#define MPJX_MOVE_KERNEL_TRANSPOSE 8u
+int mpjx_comm_last_move_kernels(mpjx_comm_t comm, unsigned *mask);
 
 /* ---- Pack, Unpack, Pack_size (Comm.Pack / Unpack / Pack_size, src/mpi/Comm.java:1860-1983) ----------------
  * `count` items of any datatype (basic, pair or derived) to and from ONE section of an mpjbuf static-buffer

@@ -43,7 +43,7 @@ inline void check(int status, const char* what) {
 // A basic type, or a (value, index) pair type SHORT2..DOUBLE2 = Contiguous(2, base)
 // (src/mpi/MPI.java:110-114): `code` crosses the C ABI; buffers are arrays of the base type,
 // offsets are base-element indices, counts are datatype elements (pairs).
-// A derived type (Contiguous, Vector, Hvector, Indexed, Hindexed) owns a code of the library's registry until Free(), as in mpiJava;
+// A derived type (Contiguous, Vector, Hvector, Indexed, Hindexed, Struct) owns a code of the library's registry until Free(), as in mpiJava;
 // copies share it.
 struct Datatype {
   int code;
@@ -53,11 +53,13 @@ struct Datatype {
   int extent = 0;    // base elements from one item to the next (0: size)
   int base = 0;      // the basic type's code (0: code & 0xff)
   bool derived = false;
-  int lb = 0;        // lowest base element of an item from its origin (mpjx_type_layout)
+  int lb = 0;        // the type's lb in base elements from an item's origin (mpjx_type_layout)
+  int ub = 0;        // and its ub, from the library (made types only: `made`)
+  bool made_ = false;  // extent, lb and ub are the library's, an extent of 0 included
   int Size() const { return size; }
-  int Extent() const { return extent ? extent : size; }
+  int Extent() const { return made_ ? extent : extent ? extent : size; }
   int Lb() const { return lb; }
-  int Ub() const { return lb + Extent(); }
+  int Ub() const { return made_ ? ub : lb + Extent(); }
   int Base() const { return base ? base : (code & 0xff); }
   void Commit() const {}
   void Free() {
@@ -91,6 +93,23 @@ struct Datatype {
                            const Datatype& oldtype) {
     return indexed(mpjx_type_hindexed, "Datatype.Hindexed", blocklengths, displacements, oldtype);
   }
+  // block i: blocklengths[i] items of types[i] from displacements[i] BASE elements; MPI::LB and MPI::UB set the
+  // bounds by the reference's order-dependent rules (src/mpi/Struct.java:149-386; include/mpjx.h)
+  static Datatype Struct(const std::vector<int>& blocklengths, const std::vector<int>& displacements,
+                         const std::vector<Datatype>& types) {
+    if (blocklengths.size() != displacements.size() || blocklengths.size() != types.size())
+      throw MPIException("Datatype.Struct: the three arrays differ in length");
+    const std::vector<int64_t> b(blocklengths.begin(), blocklengths.end()), d(displacements.begin(), displacements.end());
+    std::vector<int> codes;
+    const Datatype* data = nullptr;
+    for (const Datatype& t : types) {
+      codes.push_back(t.code);
+      if (!data && t.code != MPJX_LB && t.code != MPJX_UB) data = &t;
+    }
+    int code = 0;
+    check(mpjx_type_struct((int)b.size(), b.data(), d.data(), codes.data(), &code), "Datatype.Struct");
+    return made(code, data ? *data : Datatype{MPJX_BYTE, 1, "BYTE"}, "Struct");
+  }
   static Datatype indexed(int (*fn)(int, const int64_t*, const int64_t*, int, int*), const char* name,
                           const std::vector<int>& bl, const std::vector<int>& ds, const Datatype& oldtype) {
     if (bl.size() != ds.size()) throw MPIException(std::string(name) + ": the two arrays differ in length");
@@ -103,14 +122,14 @@ struct Datatype {
   static Datatype made(int code, const Datatype& oldtype, const char* name) {
     int base = 0;
     int64_t size = 0, extent = 0;
-    int64_t lb = 0;
+    int64_t lb = 0, ub = 0;
     check(mpjx_type_info(code, &base, &size, &extent), "mpjx_type_info");
-    check(mpjx_type_layout(code, &lb, nullptr, nullptr, nullptr), "mpjx_type_layout");
-    if (size > INT32_MAX || lb + extent > INT32_MAX) {
+    check(mpjx_type_layout(code, &lb, &ub, nullptr, nullptr), "mpjx_type_layout");
+    if (size > INT32_MAX || ub > INT32_MAX || lb < INT32_MIN || extent > INT32_MAX) {
       (void)mpjx_type_free(code);
       throw MPIException(std::string(name) + ": the type exceeds this mirror's int sizes");
     }
-    return Datatype{code, oldtype.byteSize, name, (int)size, (int)extent, base, true, (int)lb};
+    return Datatype{code, oldtype.byteSize, name, (int)size, (int)extent, base, true, (int)lb, (int)ub, true};
   }
 };
 
@@ -133,6 +152,7 @@ struct MPI {
   static constexpr Datatype LONG2{MPJX_LONG2, 8, "LONG2", 2};
   static constexpr Datatype FLOAT2{MPJX_FLOAT2, 4, "FLOAT2", 2};
   static constexpr Datatype DOUBLE2{MPJX_DOUBLE2, 8, "DOUBLE2", 2};
+  static constexpr Datatype LB{MPJX_LB, 0, "LB", 0}, UB{MPJX_UB, 0, "UB", 0};  // components of Datatype::Struct only
   static constexpr Op MAX{MPJX_MAX, "MAX"}, MIN{MPJX_MIN, "MIN"}, SUM{MPJX_SUM, "SUM"},
       PROD{MPJX_PROD, "PROD"}, LAND{MPJX_LAND, "LAND"}, BAND{MPJX_BAND, "BAND"}, LOR{MPJX_LOR, "LOR"},
       BOR{MPJX_BOR, "BOR"}, LXOR{MPJX_LXOR, "LXOR"}, BXOR{MPJX_BXOR, "BXOR"}, MAXLOC{MPJX_MAXLOC, "MAXLOC"},
@@ -155,6 +175,12 @@ class Intracomm {
   int Rank() const { return rank_; }
   int Size() const { return size_; }
   mpjx_comm_t handle() const { return c_; }
+  // the kernels this rank's last data-movement call launched: an OR of MPJX_MOVE_KERNEL_* (0: none)
+  unsigned LastMoveKernels() const {
+    unsigned m = 0;
+    check(mpjx_comm_last_move_kernels(c_, &m), "mpjx_comm_last_move_kernels");
+    return m;
+  }
   void Free() {
     if (c_) mpjx_comm_destroy(c_);
     c_ = nullptr;

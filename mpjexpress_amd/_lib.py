@@ -80,6 +80,9 @@ def _declare(L):
         "mpjx_type_indexed": ([c_int, pi64, pi64, c_int, ctypes.POINTER(c_int)], c_int),
         "mpjx_type_hindexed": ([c_int, pi64, pi64, c_int, ctypes.POINTER(c_int)], c_int),
         "mpjx_type_layout": ([c_int, pi64, pi64, pi64, ctypes.POINTER(c_int)], c_int),
+        "mpjx_type_struct": ([c_int, pi64, pi64, ctypes.POINTER(c_int), ctypes.POINTER(c_int)], c_int),
+        "mpjx_type_true_bounds": ([c_int, pi64, pi64], c_int),
+        "mpjx_comm_last_move_kernels": ([vp, ctypes.POINTER(c_uint)], c_int),
         "mpjx_type_free": ([c_int], c_int),
         "mpjx_type_info": ([c_int, ctypes.POINTER(c_int), pi64, pi64], c_int),
         "mpjx_alltoallv_dt": ([vp, vp, pi64, pi64, c_int, vp, pi64, pi64, c_int, vp], c_int),

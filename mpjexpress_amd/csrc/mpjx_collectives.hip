@@ -1669,6 +1669,7 @@ int own_mismatch(int me, const MovePlan& p) {
 }
 
 int moves_run(mpjx_comm* c, MoveKind kind, MovePlan& p, int type, void* stream) {
+  c->move_kernels = 0;
   CHK(moves_check(c, p));
   Call k;
   CHK(k.begin(c, stream, type));
@@ -1693,6 +1694,7 @@ int moves_run(mpjx_comm* c, MoveKind kind, MovePlan& p, int type, void* stream) 
       for (int j = 0; j < P; j++)    // receiver
         for (int i = 0; i < P; i++)  // sender
           ml.add((char*)all[j][1] + R(j)[i].off, (const char*)all[i][0] + S(i)[j].off, R(j)[i].len);
+      if (!ml.segs.empty()) c->move_kernels |= MPJX_MOVE_KERNEL_MOVES;
       HIPCHK(launch_moves(ml, k.s));
     }
     CHK(t->fence(k.s, true));
@@ -1701,6 +1703,7 @@ int moves_run(mpjx_comm* c, MoveKind kind, MovePlan& p, int type, void* stream) 
   {
     MoveList ml;
     ml.add(p.recv + p.R[me].off, p.send + p.S[me].off, p.R[me].len);
+    if (!ml.segs.empty()) c->move_kernels |= MPJX_MOVE_KERNEL_MOVES;
     HIPCHK(launch_moves(ml, k.s));
   }
   if (P == 1) return k.end();
@@ -1739,7 +1742,9 @@ int moves_begin(mpjx_comm* c, int type, int* esz) {
 // Indexed / Hindexed, mpjx_indexed_plan.hpp). Per rank, P send layouts and P receive layouts (SideBytes,
 // absolute addresses); a segment moves the packed bytes of a send layout in order into the matching receive
 // layout. A segment whose two layouts are contiguous runs k_moves, one whose two layouts are regular
-// k_strided (mpjx_k_strided.hip), every other one k_indexed (mpjx_k_indexed.hip), whose irregular sides read
+// k_strided (mpjx_k_strided.hip) or, where it is an element transpose (plan_transpose_seg: a contiguous run
+// against one granule per block with consecutive items on consecutive granules), k_transpose
+// (mpjx_k_transpose.hip), every other one k_indexed (mpjx_k_indexed.hip), whose irregular sides read
 // their type's device table from the launching communicator's cache (idx_table). "Strided" below means
 // "not contiguous". The engines are moves_run's:
 //   P = 1                     both types contiguous: the call IS mpjx_alltoallv's (byte ranges, moves_run);
@@ -1780,13 +1785,23 @@ struct DtMoves {
   MoveList ml;
   std::vector<StridedSeg> st;
   std::vector<IndexedSeg> ix;
-  hipError_t launch(hipStream_t s) {
+  std::vector<TransposeSeg> tp;
+  hipError_t launch(mpjx_comm* c, hipStream_t s) {
+    c->move_kernels |= (ml.segs.empty() ? 0u : MPJX_MOVE_KERNEL_MOVES) | (st.empty() ? 0u : MPJX_MOVE_KERNEL_STRIDED) |
+                       (ix.empty() ? 0u : MPJX_MOVE_KERNEL_INDEXED) | (tp.empty() ? 0u : MPJX_MOVE_KERNEL_TRANSPOSE);
     hipError_t e = launch_moves(ml, s);
     if (e == hipSuccess) e = launch_strided(st, s);
+    if (e == hipSuccess) e = launch_transpose(tp, s);
     if (e == hipSuccess) e = launch_indexed(ix, s);
     return e;
   }
 };
+
+// MPJX_TRANSPOSE=0 (read per call, like MPJX_INDEXED_LDS_MAX_BLOCKS) sends every segment back to k_strided
+bool transpose_on() {
+  const char* e = getenv("MPJX_TRANSPOSE");
+  return !(e && e[0] == '0' && e[1] == 0);
+}
 
 // The device table of an irregular layout, from c's cache: uploaded on `s` at first use. The cache entry
 // keeps the host list alive, so the copy's source outlives it.
@@ -1806,7 +1821,7 @@ int idx_table(mpjx_comm* c, const SideBytes& x, hipStream_t s, const IdxEnt** ou
   return MPJX_SUCCESS;
 }
 
-// One segment onto the lists of the three kernels
+// One segment onto the lists of the four kernels
 int dt_add(mpjx_comm* c, hipStream_t st, const SideBytes& s, const SideBytes& d, DtMoves* m) {
   if (s.total() <= 0) return MPJX_SUCCESS;
   if (s.contiguous() && d.contiguous()) {
@@ -1815,6 +1830,11 @@ int dt_add(mpjx_comm* c, hipStream_t st, const SideBytes& s, const SideBytes& d,
   }
   std::string err;
   if (s.regular() && d.regular()) {
+    TransposeSeg ts;
+    if (transpose_on() && plan_transpose_seg(s, d, &ts)) {
+      m->tp.push_back(ts);
+      return MPJX_SUCCESS;
+    }
     StridedSeg sg;
     const int rc = plan_strided_seg(s, d, &sg, &err);
     if (rc != kTypeOk) return fail(rc, "%s", err.c_str());
@@ -1840,6 +1860,7 @@ SideBytes packed_at(const char* p, int64_t bytes) {
 }
 
 int dt_run(mpjx_comm* c, DtPlan& p, void* stream) {
+  c->move_kernels = 0;
   const int P = c->size, me = c->rank;
   auto* t = dynamic_cast<SmpTransport*>(c->tr.get());
   const bool world = P > 1 && t && smp_direct(c) && t->single();
@@ -1879,14 +1900,14 @@ int dt_run(mpjx_comm* c, DtPlan& p, void* stream) {
       for (int j = 0; j < P; j++)    // receiver
         for (int i = 0; i < P; i++)  // sender
           DCHK(dt_add(c, k.s, S(i)[(size_t)j], R(j)[(size_t)i], &mv));
-      HIPCHK(mv.launch(k.s));
+      HIPCHK(mv.launch(c, k.s));
     }
     CHK(t->fence(k.s, true));
     return k.end();
   }
   CHK(dt_add(c, k.s, p.S[(size_t)me], p.R[(size_t)me], &mv));
   if (P == 1) {
-    HIPCHK(mv.launch(k.s));
+    HIPCHK(mv.launch(c, k.s));
     return k.end();
   }
   // scratch slots (16-B aligned) of the strided sends, then of the strided receives
@@ -1919,9 +1940,9 @@ int dt_run(mpjx_comm* c, DtPlan& p, void* stream) {
       recvs.push_back({j, at, (size_t)r.total()});
     }
   }
-  HIPCHK(mv.launch(k.s));  // the own block and every peer's pack: one launch per kernel per table
+  HIPCHK(mv.launch(c, k.s));  // the own block and every peer's pack: one launch per kernel per table
   CHK(c->tr->exchange(sends, recvs, k.s));
-  HIPCHK(unpack.launch(k.s));
+  HIPCHK(unpack.launch(c, k.s));
   return k.end();
 }
 
@@ -1985,6 +2006,12 @@ static int pack_entry(mpjx_comm_t c, bool unpack, const void* buf, int64_t count
                 type);
   SideBytes lay;
   if (!plan_side(f, (uint64_t)(uintptr_t)buf, count, 0, &lay, &err)) return fail(MPJX_ERR_ARG, "%s: %s", who, err.c_str());
+  if (unpack && lay.items_may_overlap()) {  // items closer together than their blocks reach (an explicit extent)
+    int a = 0, b = 0;
+    if (strided_overlap({}, {lay}, &a, &b) == kRecvOverlap)
+      return fail(MPJX_ERR_ARG, "%s: %lld items of datatype %d (extent %lld) share a byte: they can be packed, not "
+                  "unpacked into", who, (long long)count, type, (long long)f.extent());
+  }
   if (!c) return fail(MPJX_ERR_ARG, "%s: comm is NULL", who);
   if (sec.words > 0) CHK(check_dev_ptr(buf, unpack ? "outbuf" : "inbuf"));
   CHK(check_dev_ptr(image, "image"));
@@ -2273,7 +2300,7 @@ int rd_direct(Call& k, const RdCall& q, const std::vector<const RdCall*>& all) {
   if (alias) {
     DtMoves mv;
     for (int r = 0; r < P; r++) CHK(dt_add(c, k.s, rebased(q.S, q.send, res[r]), rebased(q.S, q.send, out[r]), &mv));
-    HIPCHK(mv.launch(k.s));
+    HIPCHK(mv.launch(c, k.s));
   }
   return MPJX_SUCCESS;
 }
@@ -2301,6 +2328,7 @@ int rd_run(mpjx_comm* c, RdCall& q, int type, void* stream) {
   if (q.f.irr && q.f.irr->self_overlap)
     return reject(c, fail(MPJX_ERR_ARG, "datatype %d has blocks that share a byte: a reduction receives into it", type));
   if (!c) return fail(MPJX_ERR_ARG, "comm is NULL");
+  c->move_kernels = 0;
   const int P = c->size, me = c->rank;
   const int64_t count = q.mine;  // as passed (Reduce_scatter: unused)
   if (q.kind == RD_REDUCE) CHK(check_root(c, q.root));
@@ -2339,6 +2367,17 @@ int rd_run(mpjx_comm* c, RdCall& q, int type, void* stream) {
       q.badmsg = msg;
     }
   }
+  // items closer together than their blocks reach (an explicit extent): the receive layout may overlap itself
+  if (rb > 0 && !q.bad && q.R.items_may_overlap()) {
+    int a = 0, b = 0;
+    if (strided_overlap({}, {q.R}, &a, &b) == kRecvOverlap) {
+      q.bad = MPJX_ERR_ARG;
+      char msg[256];
+      snprintf(msg, sizeof msg, "rank %d: %lld items of datatype %d (extent %lld) share a byte: a reduction receives "
+               "into them", me, (long long)q.mine, type, (long long)q.f.extent());
+      q.badmsg = msg;
+    }
+  }
   const bool blocking = (q.flags & MPJX_FLAG_BLOCKING) != 0;
   Call k;
   if (P == 1) {
@@ -2349,7 +2388,7 @@ int rd_run(mpjx_comm* c, RdCall& q, int type, void* stream) {
     if (rb > 0 && (const char*)q.recv != q.send) {
       DtMoves mv;
       CHK(dt_add(c, k.s, q.S, q.R, &mv));
-      HIPCHK(mv.launch(k.s));
+      HIPCHK(mv.launch(c, k.s));
     }
     CHK(k.end());
     return finish_blocking(c, q.flags, stream);
@@ -2417,14 +2456,14 @@ int rd_run(mpjx_comm* c, RdCall& q, int type, void* stream) {
   if (pack) {
     DtMoves mv;
     CHK(dt_add(c, k.s, q.S, packed_at(ps, sb), &mv));
-    HIPCHK(mv.launch(k.s));
+    HIPCHK(mv.launch(c, k.s));
   }
   CHK(k.end());
   CHK(rd_inner(c, q, ps, pr, q.flags & ~MPJX_FLAG_BLOCKING, k.s));
   if (unpack) {
     DtMoves mv;
     CHK(dt_add(c, k.s, packed_at(pr, rb), q.R, &mv));
-    HIPCHK(mv.launch(k.s));
+    HIPCHK(mv.launch(c, k.s));
   }
   CHK(k.end());
   return finish_blocking(c, q.flags, stream);
@@ -2547,6 +2586,13 @@ extern "C" int mpjx_reduce_scatter_dt(mpjx_comm_t c, const void* sendbuf, void* 
 extern "C" int mpjx_scan_dt(mpjx_comm_t c, const void* sendbuf, void* recvbuf, int64_t count, int type, int op,
                             unsigned flags, void* stream) {
   return ended(c, rd_call(c, RD_SCAN, sendbuf, recvbuf, count, nullptr, type, op, 0, flags, stream));
+}
+
+extern "C" int mpjx_comm_last_move_kernels(mpjx_comm_t c, unsigned* mask) {
+  COMM_ARG(c);
+  if (!mask) return fail(MPJX_ERR_ARG, "NULL argument");
+  *mask = c->move_kernels;
+  return MPJX_SUCCESS;
 }
 
 extern "C" int mpjx_comm_last_dt_form(mpjx_comm_t c, int* form) {

@@ -75,7 +75,7 @@ extern "C" int mpjx_type_contiguous(int64_t count, int oldtype, int* newtype) {
   TypeForm old, f;
   if (!type_form(oldtype, &old)) return fail(MPJX_ERR_ARG, "unknown or freed datatype code %d", oldtype);
   std::string err;
-  const int rc = contiguous_of(count, old, &f, &err);
+  const int rc = contiguous_any_form(count, old, &f, &err);
   f.pair = old.pair;
   return type_new(rc, f, err, "Contiguous", newtype);
 }
@@ -85,7 +85,7 @@ extern "C" int mpjx_type_vector(int64_t count, int64_t blocklength, int64_t stri
   TypeForm old, f;
   if (!type_form(oldtype, &old)) return fail(MPJX_ERR_ARG, "unknown or freed datatype code %d", oldtype);
   std::string err;
-  const int rc = vector_form(count, blocklength, stride, old, &f, &err);
+  const int rc = vector_any_form(count, blocklength, stride, old, &f, &err);
   f.pair = old.pair;
   return type_new(rc, f, err, "Vector", newtype);
 }
@@ -123,6 +123,22 @@ extern "C" int mpjx_type_hindexed(int n, const int64_t* blocklengths, const int6
   return type_new(rc, f, err, "Hindexed", newtype);
 }
 
+// Struct (mpjx_indexed_plan.hpp: struct_form): the one constructor that takes the markers MPJX_LB / MPJX_UB
+extern "C" int mpjx_type_struct(int n, const int64_t* blocklengths, const int64_t* displacements, const int* types,
+                                int* newtype) {
+  if (!newtype) return fail(MPJX_ERR_ARG, "NULL argument");
+  if (n < 0) return fail(MPJX_ERR_ARG, "Struct: negative n %d", n);
+  if (n > 0 && !types) return fail(MPJX_ERR_ARG, "Struct: NULL types with n = %d", n);
+  std::vector<TypeForm> comp((size_t)n);
+  for (int i = 0; i < n; i++)
+    if (!type_form(types[i], &comp[(size_t)i], true))
+      return fail(MPJX_ERR_ARG, "Struct: unknown or freed datatype code %d at index %d", types[i], i);
+  TypeForm f;
+  std::string err;
+  const int rc = struct_form(n, blocklengths, displacements, comp, &f, &err);
+  return type_new(rc, f, err, "Struct", newtype);
+}
+
 extern "C" int mpjx_type_layout(int type, int64_t* lb, int64_t* ub, int64_t* nblocks, int* regular) {
   TypeForm f;
   if (!type_form(type, &f)) return fail(MPJX_ERR_ARG, "unknown or freed datatype code %d", type);
@@ -130,6 +146,14 @@ extern "C" int mpjx_type_layout(int type, int64_t* lb, int64_t* ub, int64_t* nbl
   if (ub) *ub = f.ub();
   if (nblocks) *nblocks = f.merged_blocks();
   if (regular) *regular = f.irr ? 0 : 1;
+  return MPJX_SUCCESS;
+}
+
+extern "C" int mpjx_type_true_bounds(int type, int64_t* true_lb, int64_t* true_ub) {
+  TypeForm f;
+  if (!type_form(type, &f)) return fail(MPJX_ERR_ARG, "unknown or freed datatype code %d", type);
+  if (true_lb) *true_lb = f.size() > 0 ? f.true_lb() : 0;
+  if (true_ub) *true_ub = f.size() > 0 ? f.true_ub() : 0;
   return MPJX_SUCCESS;
 }
 

@@ -294,6 +294,8 @@ struct mpjx_comm {
   // path, the temporaries of the direct FT Allreduce — apart from `scratch`, which the contiguous bodies
   // carve; grown on demand and kept until the communicator is destroyed, as hstage is
   int dt_form = 0;
+  // the kernels this rank's last data-movement call launched (mpjx_comm_last_move_kernels, MPJX_MOVE_KERNEL_*)
+  unsigned move_kernels = 0;
   char* dtstage = nullptr;
   size_t dtstage_bytes = 0;
   // Device buffers outgrown during the communicator's life, freed only by mpjx_comm_destroy. Growing

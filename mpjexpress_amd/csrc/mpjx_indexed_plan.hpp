@@ -1,7 +1,7 @@
-// mpjx_indexed_plan.hpp — the irregular derived datatypes (Hvector, Indexed, Hindexed) and the host-side
-// planning of k_indexed (mpjx_k_indexed.hip). No HIP include: plain C++17, compiled, tested and sanitized on
-// the CPU (tests/cpp/indexed_plan_test.cpp); the kernel includes the same header, so the address function the
-// test walks is the one the kernel runs.
+// mpjx_indexed_plan.hpp — the irregular derived datatypes (Hvector, Indexed, Hindexed, Struct with the LB / UB
+// markers: struct_form, BoundsAcc) and the host-side planning of k_indexed (mpjx_k_indexed.hip). No HIP include:
+// plain C++17, compiled, tested and sanitized on the CPU (tests/cpp/indexed_plan_test.cpp); the kernel includes
+// the same header, so the address function the test walks is the one the kernel runs.
 //
 // An irregular type is a list of blocks (offset, length) in base elements from the item's origin, in PACK
 // order: the order of the constructor's arrays, as Indexed.IndexedPacker.pack walks them, not address order
@@ -42,10 +42,19 @@ struct ElemBlock {
   int64_t off, len;  // base elements
 };
 
-// The form of `blocks` (pack order, merged, none empty) with bounds lb, ub: regular where the list is.
-inline void normal_form(const TypeForm& old, const std::vector<ElemBlock>& v, int64_t lb, int64_t ub, TypeForm* out) {
+// The form of `blocks` (pack order, merged, none empty), regular where the list is, with the reference's bounds
+// lb, ub and sticky flags (TypeForm::set_bounds: kept apart only where they are not the blocks' own). The
+// irregular layout's own lb and ub are the blocks' — the lowest and one past the highest element touched —
+// which is what SideBytes::span() reports.
+inline void normal_form(const TypeForm& old, const std::vector<ElemBlock>& v, int64_t rlb, int64_t rub, bool lbs,
+                        bool ubs, TypeForm* out) {
   *out = contiguous_form(old.base, old.bsz, 0);
-  if (v.empty()) return;
+  if (v.empty()) {
+    out->set_bounds(rlb, rub, lbs, ubs);
+    return;
+  }
+  int64_t lb = v[0].off, ub = v[0].off + v[0].len;
+  for (const ElemBlock& b : v) lb = std::min(lb, b.off), ub = std::max(ub, b.off + b.len);
   bool reg = v[0].off == 0;
   const int64_t st = v.size() > 1 ? v[1].off - v[0].off : v[0].len;
   for (size_t i = 1; reg && i < v.size(); i++) reg = v[i].len == v[0].len && v[i].off - v[i - 1].off == st;
@@ -53,6 +62,7 @@ inline void normal_form(const TypeForm& old, const std::vector<ElemBlock>& v, in
     out->nblocks = (int64_t)v.size();
     out->blocklen = v[0].len;
     out->stride = st;
+    out->set_bounds(rlb, rub, lbs, ubs);
     return;
   }
   auto irr = std::make_shared<IrrLayout>();
@@ -72,41 +82,86 @@ inline void normal_form(const TypeForm& old, const std::vector<ElemBlock>& v, in
   std::sort(s.begin(), s.end(), [](const ElemBlock& a, const ElemBlock& b) { return a.off < b.off; });
   for (size_t i = 1; i < s.size() && !irr->self_overlap; i++) irr->self_overlap = s[i - 1].off + s[i - 1].len > s[i].off;
   out->irr = irr;
+  out->set_bounds(rlb, rub, lbs, ubs);
 }
 
-// n blocks: block i is bl(i) items of `old`, old.extent apart, starting start(i) base elements from the
-// origin.
-template <class BL, class ST>
-inline int irregular_form(int64_t n, BL bl, ST start, const TypeForm& old, TypeForm* out, std::string* err) {
+// The bounds of a type from its blocks, by the reference's rules. Indexed / Hindexed / Vector / Hvector /
+// Contiguous take the minimum and maximum over their blocks and hand the oldtype's sticky flags on
+// (Indexed.java:110-177, Vector.java:99-135, Contiguous.java:71-98 — the three agree for the positive strides
+// built here). Struct restates Struct.computeBounds (Struct.java:149-386) AS WRITTEN, in the order of the
+// arrays: a component with ubSet REPLACES ub (the `if (max_ub > ub)` test is commented out at :243), one
+// without moves ub whenever it reaches past every earlier unmarked component (trueUb, :251-258), even after a
+// marker; lb mirrors it (:272-303). A marker is itself an unmarked component for the OTHER bound.
+struct BoundsAcc {
   using i128 = __int128;
-  const i128 lim = kMoveMaxBytes / old.bsz;
-  const int64_t onb = form_nblocks(old), osz = old.size(), oext = old.extent();
+  bool strukt = false;
+  bool any = false, have_tlb = false, have_tub = false, lbs = false, ubs = false;
+  i128 lb = 0, ub = 0, tlb = 0, tub = 0;
+  // `len` > 0 items of `old` (with data, or with a sticky flag), the first `st` base elements from the origin
+  void add(i128 st, int64_t len, const TypeForm& old) {
+    const i128 max_ub = st + (i128)(len - 1) * old.extent() + old.ub(), min_lb = st + old.lb();
+    if (!strukt) {
+      lb = any ? std::min(lb, min_lb) : min_lb;
+      ub = any ? std::max(ub, max_ub) : max_ub;
+      lbs = lbs || old.lb_set, ubs = ubs || old.ub_set;
+      any = true;
+      return;
+    }
+    any = true;
+    if (old.ub_set) {
+      ubs = true;
+      ub = max_ub;
+    } else if (!have_tub || max_ub > tub) {
+      have_tub = true;
+      tub = max_ub;
+      ub = std::max(max_ub, st);
+    }
+    if (old.lb_set) {
+      lbs = true;
+      lb = min_lb;
+    } else if (!have_tlb || min_lb < tlb) {
+      have_tlb = true;
+      tlb = min_lb;
+      lb = std::min(min_lb, st);
+    }
+  }
+};
+
+// n blocks: block i is bl(i) items of oldf(i), one extent of that type apart, starting start(i) base elements
+// from the origin. `proto` gives the new type's base element; `strukt` selects Struct's bounds rules.
+template <class BL, class ST, class OF>
+inline int flatten_form(int64_t n, BL bl, ST start, OF oldf, const TypeForm& proto, bool strukt, TypeForm* out,
+                        std::string* err) {
+  using i128 = __int128;
+  const i128 lim = kMoveMaxBytes / proto.bsz;
   std::vector<ElemBlock> v;
-  i128 size = 0, lb = 0, ub = 0;
-  bool any = false;
+  i128 size = 0;
+  BoundsAcc acc;
+  acc.strukt = strukt;
   for (int64_t i = 0; i < n; i++)
     if (bl(i) < 0) {
       *err = "negative blocklength " + std::to_string(bl(i)) + " at index " + std::to_string(i);
       return kTypeErrArg;
     }
   for (int64_t i = 0; i < n; i++) {
+    const TypeForm& old = oldf(i);
     const int64_t len = bl(i);
-    if (len == 0 || osz == 0) continue;
+    const int64_t onb = form_nblocks(old), osz = old.size(), oext = old.extent();
+    if (len == 0 || (osz == 0 && !old.lb_set && !old.ub_set)) continue;
     const i128 st = start(i);
-    if (st < 0) {
+    if (st < 0 && osz != 0) {
       *err = "a negative displacement (" + std::to_string((long long)st) + " base elements at index " +
              std::to_string(i) + ") is not supported";
       return kTypeErrUnsupported;
     }
-    const i128 hi = st + (i128)(len - 1) * oext + old.ub();
+    const i128 hi = st + (i128)(len - 1) * oext + std::max(old.ub(), old.true_ub());
     size += (i128)len * osz;
-    if (st > lim || hi > lim || size > lim) {
+    if (st > lim || st < -lim || hi > lim || size > lim || old.lb() < -lim) {
       *err = "block " + std::to_string(i) + " (length " + std::to_string(len) + ") reaches beyond 2^62 bytes";
       return kTypeErrArg;
     }
-    lb = any ? std::min(lb, st + old.lb()) : st + old.lb();
-    ub = any ? std::max(ub, hi) : hi;
-    any = true;
+    acc.add(st, len, old);
+    if (osz == 0) continue;  // a marker, or a type of markers only: bounds, no data
     auto push = [&](int64_t off, int64_t l) {
       if (!v.empty() && v.back().off + v.back().len == off) {
         v.back().len += l;
@@ -117,11 +172,11 @@ inline int irregular_form(int64_t n, BL bl, ST start, const TypeForm& old, TypeF
       return true;
     };
     bool fits = true;
-    if (onb == 1) {  // one block per item of old: its extent is its length, so the run is one block
-      int64_t o, l;
-      form_block(old, 0, &o, &l);
-      fits = push((int64_t)st + o, len * l);
-    } else {  // every item adds at least onb - 1 >= 1 merged blocks: the loop ends at the bound
+    int64_t o0, l0;
+    form_block(old, 0, &o0, &l0);
+    if (onb == 1 && oext == l0) {  // one block per item of old and the items abut: the run is one block
+      fits = push((int64_t)st + o0, len * l0);
+    } else {  // every item adds at least one merged block: the loop ends at the bound
       for (int64_t j = 0; j < len && fits; j++)
         for (int64_t b = 0; b < onb && fits; b++) {
           int64_t o, l;
@@ -135,8 +190,19 @@ inline int irregular_form(int64_t n, BL bl, ST start, const TypeForm& old, TypeF
       return kTypeErrUnsupported;
     }
   }
-  normal_form(old, v, (int64_t)lb, (int64_t)ub, out);
+  if (acc.ub < acc.lb) {
+    *err = "an explicit extent below 0 (lb " + std::to_string((long long)acc.lb) + ", ub " +
+           std::to_string((long long)acc.ub) + ": extent " + std::to_string((long long)(acc.ub - acc.lb)) +
+           ") is not supported";
+    return kTypeErrUnsupported;
+  }
+  normal_form(proto, v, (int64_t)acc.lb, (int64_t)acc.ub, acc.lbs, acc.ubs, out);
   return kTypeOk;
+}
+
+template <class BL, class ST>
+inline int irregular_form(int64_t n, BL bl, ST start, const TypeForm& old, TypeForm* out, std::string* err) {
+  return flatten_form(n, bl, start, [&](int64_t) -> const TypeForm& { return old; }, old, false, out, err);
 }
 
 inline int indexed_args(int64_t n, const int64_t* bl, const int64_t* disp, std::string* err) {
@@ -200,6 +266,62 @@ inline int hvector_form(int64_t count, int64_t blocklength, int64_t stride, cons
   }
   return irregular_form(count, [&](int64_t) { return blocklength; }, [&](int64_t j) { return (__int128)j * stride; }, old,
                         out, err);
+}
+
+// Vector and Contiguous of any oldtype. An oldtype with explicit bounds (its extent is not its blocks' span) makes
+// layouts the regular planner of mpjx_strided_plan.hpp cannot express, a Vector of a resized element for one: it
+// is flattened here, as the Hvector of stride * old.extent; the result is regular again where its blocks are.
+// Every other oldtype keeps vector_form, its limits included.
+inline int vector_any_form(int64_t count, int64_t blocklength, int64_t stride, const TypeForm& old, TypeForm* out,
+                           std::string* err) {
+  if (!old.bounds) return vector_form(count, blocklength, stride, old, out, err);
+  if (count < 0 || blocklength < 0) {
+    *err = std::string("negative ") + (count < 0 ? "count" : "blocklength");
+    return kTypeErrArg;
+  }
+  const __int128 hs = (__int128)stride * old.extent();
+  if (hs > kMoveMaxBytes || hs < -kMoveMaxBytes) {
+    *err = "count or stride too large";
+    return kTypeErrArg;
+  }
+  return hvector_form(count, blocklength, (int64_t)hs, old, out, err);
+}
+inline int contiguous_any_form(int64_t count, const TypeForm& old, TypeForm* out, std::string* err) {
+  if (!old.bounds) return contiguous_of(count, old, out, err);
+  if (count < 0) {
+    *err = "negative count";
+    return kTypeErrArg;
+  }
+  // Contiguous.java:77-98: lb = old.lb, ub = lb + count * old.extent, which is the one block of `count` items
+  return irregular_form(count > 0 ? 1 : 0, [&](int64_t) { return count; }, [&](int64_t) { return (__int128)0; }, old,
+                        out, err);
+}
+
+// Struct(bl[], disp[], types[]): block i is bl[i] items of comp[i], one extent of that type apart, starting
+// disp[i] BASE elements from the origin, packed in the order of the arrays (Struct.StructPacker.pack,
+// Struct.java:448-464). A marker (MPJX_LB, MPJX_UB) has no base type and no data; every other component must
+// have the one base type (Struct.java:100-117). The bounds are BoundsAcc's Struct rules.
+inline int struct_form(int64_t n, const int64_t* bl, const int64_t* disp, const std::vector<TypeForm>& comp,
+                       TypeForm* out, std::string* err) {
+  const int rc = indexed_args(n, bl, disp, err);
+  if (rc != kTypeOk) return rc;
+  TypeForm proto = contiguous_form(0, 1, 0);
+  bool pair = true;
+  for (int64_t i = 0; i < n; i++) {
+    const TypeForm& c = comp[(size_t)i];
+    if (c.marker()) continue;
+    if (proto.base == 0) proto.base = c.base, proto.bsz = c.bsz;
+    else if (proto.base != c.base) {
+      *err = "Base types of all component types in a Struct must agree (base type " + std::to_string(proto.base) +
+             ", then " + std::to_string(c.base) + " at index " + std::to_string(i) + ")";
+      return kTypeErrArg;
+    }
+    pair = pair && c.pair;
+  }
+  const int frc = flatten_form(n, [&](int64_t i) { return bl[i]; }, [&](int64_t i) { return (__int128)disp[i]; },
+                               [&](int64_t i) -> const TypeForm& { return comp[(size_t)i]; }, proto, true, out, err);
+  if (frc == kTypeOk) out->pair = pair && proto.base != 0;
+  return frc;
 }
 
 // ---- the descriptor the kernel reads --------------------------------------------------------------------------

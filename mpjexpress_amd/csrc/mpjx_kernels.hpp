@@ -33,6 +33,7 @@
 #include "mpjx_indexed_plan.hpp"
 #include "mpjx_pack_plan.hpp"
 #include "mpjx_strided_plan.hpp"
+#include "mpjx_transpose_plan.hpp"
 
 namespace mpjx {
 
@@ -654,6 +655,10 @@ hipError_t launch_strided(const std::vector<StridedSeg>& segs, hipStream_t s);
 // The same for moves with an irregular layout on either side (mpjx_k_indexed.hip): segments planned by
 // plan_indexed_seg, their device tables uploaded on `s` or earlier; kIndexedMax segments per launch.
 hipError_t launch_indexed(const std::vector<IndexedSeg>& segs, hipStream_t s);
+
+// The element transposes among them (mpjx_k_transpose.hip): segments planned by plan_transpose_seg; kTransposeMax
+// segments per launch.
+hipError_t launch_transpose(const std::vector<TransposeSeg>& segs, hipStream_t s);
 
 // One mpjbuf section packed from (unpack: unpacked into) a buffer of any layout (mpjx_k_pack.hip): the descriptor
 // planned by plan_pack_seg, an irregular layout's device table uploaded on `s` or earlier. One launch.

@@ -99,6 +99,7 @@ inline DtRange reduce_dt_range(int64_t item0, int64_t nitems, int64_t size_bytes
 // threads create their own types)
 inline bool same_form(const TypeForm& a, const TypeForm& b) {
   if (a.base != b.base || a.bsz != b.bsz || a.pair != b.pair || !a.irr != !b.irr) return false;
+  if (a.lb() != b.lb() || a.ub() != b.ub()) return false;  // an explicit extent moves the items
   if (!a.irr) return a.nblocks == b.nblocks && a.blocklen == b.blocklen && a.stride == b.stride;
   const IrrLayout &x = *a.irr, &y = *b.irr;
   return x.size == y.size && x.lb == y.lb && x.ub == y.ub && x.tab.size() == y.tab.size() &&

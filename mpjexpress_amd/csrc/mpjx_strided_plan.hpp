@@ -58,22 +58,39 @@ struct IrrLayout {
   int64_t len(size_t b) const { return (int64_t)((b + 1 < tab.size() ? tab[b + 1].pre : (uint64_t)size) - tab[b].pre); }
 };
 
-// In elements of the base type. Regular (irr == nullptr): nblocks x blocklen at one stride, lb = 0; contiguous
+// In elements of the base type. Regular (irr == nullptr): nblocks x blocklen at one stride, data from 0; contiguous
 // types (nblocks <= 1) have stride == blocklen. Irregular: irr holds the blocks; nblocks/blocklen/stride are 0.
+// The bounds are the blocks' own (lb = the lowest element, ub = one past the highest) unless `bounds` is set:
+// then xlb / xub are the reference's lb and ub (an LB or UB marker of a Struct, or a type made from one that has
+// them), lb_set / ub_set its sticky flags, and extent() = xub - xlb is any value >= 0, whatever the blocks
+// span. Item k of a message still starts k * extent() after the origin and lb is not subtracted.
 struct TypeForm {
-  int base = 0;      // basic code 1..8
+  int base = 0;      // basic code 1..8 (0: a marker, or a Struct of markers only)
   int bsz = 0;       // bytes per base element
   int64_t nblocks = 0, blocklen = 0, stride = 0;
   std::shared_ptr<const IrrLayout> irr;
   int code = 0;      // the code the form was looked up by (type_form); keys the device-table caches
   bool pair = false; // made of (value, index) pair items: what MAXLOC / MINLOC reduce (the type constructors of
                      // mpjx_core.hip hand it on from the oldtype; the moves do not read it)
+  bool bounds = false, lb_set = false, ub_set = false;
+  int64_t xlb = 0, xub = 0;
   int64_t size() const { return irr ? irr->size / bsz : nblocks * blocklen; }
-  int64_t lb() const { return irr ? irr->lb / bsz : 0; }
-  int64_t ub() const { return irr ? irr->ub / bsz : extent(); }
-  int64_t extent() const { return irr ? (irr->ub - irr->lb) / bsz : nblocks > 0 ? (nblocks - 1) * stride + blocklen : 0; }
+  // the lowest element and one past the highest element of one item's data, from its origin
+  int64_t true_lb() const { return irr ? irr->lb / bsz : 0; }
+  int64_t true_ub() const { return irr ? irr->ub / bsz : nblocks > 0 ? (nblocks - 1) * stride + blocklen : 0; }
+  int64_t lb() const { return bounds ? xlb : true_lb(); }
+  int64_t ub() const { return bounds ? xub : true_ub(); }
+  int64_t extent() const { return ub() - lb(); }
   bool contiguous() const { return !irr && nblocks <= 1; }
   int64_t merged_blocks() const { return irr ? (int64_t)irr->tab.size() : nblocks; }
+  bool marker() const { return base == 0; }
+  // The reference's bounds: kept apart only where they are not the blocks' own, so that every type the five
+  // older constructors make from basic types is the form it always was
+  void set_bounds(int64_t lb, int64_t ub, bool lbs, bool ubs) {
+    bounds = lbs || ubs || lb != true_lb() || ub != true_ub();
+    lb_set = lbs, ub_set = ubs;
+    xlb = bounds ? lb : 0, xub = bounds ? ub : 0;
+  }
 };
 
 inline TypeForm contiguous_form(int base, int bsz, int64_t n) {
@@ -84,11 +101,19 @@ inline TypeForm contiguous_form(int base, int bsz, int64_t n) {
   return f;
 }
 
-// The form of a basic code (1..8) or a pair code (0x100 | base, base in {3, 5, 6, 7, 8}); false if neither.
+constexpr int kCodeLB = 10, kCodeUB = 11;  // MPJX_LB / MPJX_UB (Datatype.java:68-69)
+
+// The form of a basic code (1..8), a pair code (0x100 | base, base in {3, 5, 6, 7, 8}) or a marker (LB, UB: no
+// base type, size 0, lb = ub = 0 with lbSet or ubSet, BasicType.java:145-170); false if none of them.
 inline bool basic_form(int code, TypeForm* out) {
   static const int bytes[9] = {0, 1, 2, 2, 1, 4, 8, 4, 8};  // BYTE CHAR SHORT BOOLEAN INT LONG FLOAT DOUBLE
   if (code >= 1 && code <= 8) {
     *out = contiguous_form(code, bytes[code], 1);
+    return true;
+  }
+  if (code == kCodeLB || code == kCodeUB) {
+    *out = contiguous_form(0, 1, 0);
+    out->set_bounds(0, 0, code == kCodeLB, code == kCodeUB);
     return true;
   }
   const int b = code & 0xff;
@@ -195,8 +220,9 @@ class TypeRegistry {
   std::vector<Slot> slots_;
 };
 
-// Basic, pair and live derived codes
-inline bool type_form(int code, TypeForm* out) {
+// Basic, pair and live derived codes; the markers only where `markers` says so (a component of a Struct)
+inline bool type_form(int code, TypeForm* out, bool markers = false) {
+  if (!markers && (code == kCodeLB || code == kCodeUB)) return false;
   if (!(code >= kDerivedBase ? TypeRegistry::get().find(code, out) : basic_form(code, out))) return false;
   out->code = code;
   return true;
@@ -229,7 +255,17 @@ struct SideBytes {
     const int64_t blk = p / bb, w = p % bb;
     return base + (uint64_t)((blk / nb) * eb + (blk % nb) * sb + w);
   }
-  // First and one-past-last byte address touched (first == last when empty)
+  // Consecutive items may share a byte: an item's blocks reach past the next item's origin (an explicit extent
+  // below the blocks' span) and the cheap argument that they merely interleave — a regular side whose items all
+  // fit before its second block, as the columns of a panel do — does not hold. Only the exact check can tell.
+  bool items_may_overlap() const {
+    if (items <= 1 || total() <= 0) return false;
+    if (irr) return eb < irr->ub - irr->lb;
+    if (eb >= (nb - 1) * sb + bb) return false;
+    return !(eb >= bb && (items - 1) * eb + bb <= sb);
+  }
+  // First and one-past-last byte address touched (first == last when empty): the blocks' own bounds, whatever
+  // the type's lb and ub say (eb >= 0, so the last item reaches highest)
   void span(uint64_t* lo, uint64_t* hi) const {
     *lo = *hi = base;
     if (total() <= 0) return;
@@ -258,11 +294,19 @@ inline bool plan_side(const TypeForm& f, uint64_t buf, int64_t count, int64_t di
   }
   out->base = buf + (uint64_t)(disp * f.bsz);
   if (count == 0 || f.size() == 0) return true;
-  if (count > (lim - f.lb()) / f.extent()) {
+  // the last item's highest element, (count - 1) * extent + true_ub, stays within the limit (true_ub <= lim
+  // by construction; extent 0 puts every item at the same place)
+  const int64_t ext = f.extent();
+  if (ext > 0 && count - 1 > (lim - f.true_ub()) / ext) {
     *err = std::string(what) + " too large";
     return false;
   }
-  if (f.irr && f.irr->tab.size() == 1) {  // one block lb elements in: extent == size, the items abut
+  if (count > lim / f.size()) {
+    *err = std::string(what) + " too large";
+    return false;
+  }
+  const bool abut = ext == f.size();  // consecutive items of a one-block type form one run
+  if (f.irr && f.irr->tab.size() == 1 && (abut || count == 1)) {  // one block lb elements in
     out->base += (uint64_t)f.irr->tab[0].off;
     out->bb = out->sb = out->eb = count * f.irr->size;
     out->nb = out->items = 1;
@@ -270,9 +314,9 @@ inline bool plan_side(const TypeForm& f, uint64_t buf, int64_t count, int64_t di
     out->irr = f.irr;
     out->code = f.code;
     out->nb = (int64_t)f.irr->tab.size();
-    out->eb = f.extent() * f.bsz;
+    out->eb = ext * f.bsz;
     out->items = count;
-  } else if (f.contiguous() || count * f.nblocks == 1) {
+  } else if ((f.contiguous() && abut) || count * f.nblocks == 1) {
     out->bb = out->sb = out->eb = count * f.size() * f.bsz;
     out->nb = out->items = 1;
   } else {
@@ -333,7 +377,7 @@ MPJX_HD inline uint64_t strided_addr(const StridedSide& x, uint32_t q, uint32_t 
 
 // log2 of the largest power of two <= 16 that divides both sides' block bytes, strides, extents and bases
 inline uint64_t side_align_mask(const SideBytes& x) {
-  return x.base | (x.irr ? x.irr->amask : (uint64_t)x.bb | (uint64_t)x.sb | (uint64_t)x.eb);
+  return x.base | (uint64_t)x.eb | (x.irr ? x.irr->amask : (uint64_t)x.bb | (uint64_t)x.sb);
 }
 // (an irregular side gives its every block offset and length and its extent: mpjx_indexed_plan.hpp)
 inline uint32_t strided_granule_log(const SideBytes& s, const SideBytes& d) {
@@ -460,6 +504,7 @@ inline bool spans_disjoint(const std::vector<SideBytes>& S, const std::vector<Si
   for (int k = 0; k < 2; k++)
     for (const SideBytes& x : k ? R : S) {
       if (x.total() <= 0) continue;
+      if (k == 1 && x.items_may_overlap()) return false;  // a receive layout that may overlap itself
       Span sp{0, 0, k == 1};
       x.span(&sp.lo, &sp.hi);
       v.push_back(sp);

@@ -51,21 +51,27 @@ class Datatype:
         self.np_dtype = np.dtype(np_dtype)
         self.torch_dtype_name = torch_dtype_name
         self.size = size
-        self.code = base_type if size == 1 else (0x100 | base_type)
+        self.marker = size == 0  # MPI.LB / MPI.UB
+        self.code = base_type if size <= 1 else (0x100 | base_type)
         self.baseSize = self.np_dtype.itemsize
         self.byteSize = self.baseSize * size
         self.extent = size  # base elements from one item to the next
-        self.lb = 0  # lowest base element of an item from its origin (> 0 only for Hvector/Indexed/Hindexed)
+        self.lb = 0  # the type's lb in base elements from an item's origin (0 for basic and regular types)
+        self.ub = size  # and its ub: from the library for a derived type, never lb + extent computed here
+        self.true_ub = size  # one past the highest base element an item touches (the ub unless bounds are explicit)
         self.derived = False
 
     @classmethod
     def _derived(cls, code, old, name):
         """The Datatype of a derived code the library handed out (mpjx_type_*)."""
         base, size, extent, lb = ctypes.c_int(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        ub, tub = ctypes.c_int64(), ctypes.c_int64()
         _wrap("mpjx_type_info", code, ctypes.byref(base), ctypes.byref(size), ctypes.byref(extent))
-        _wrap("mpjx_type_layout", code, ctypes.byref(lb), None, None, None)
+        _wrap("mpjx_type_layout", code, ctypes.byref(lb), ctypes.byref(ub), None, None)
+        _wrap("mpjx_type_true_bounds", code, None, ctypes.byref(tub))
         dt = cls(base.value, name, old.np_dtype, old.torch_dtype_name)
         dt.size, dt.extent, dt.lb, dt.code, dt.derived = size.value, extent.value, lb.value, code, True
+        dt.ub, dt.true_ub = ub.value, tub.value
         dt.byteSize = dt.baseSize * dt.size
         return dt
 
@@ -113,6 +119,22 @@ class Datatype:
         """Datatype.Hindexed (src/mpi/Hindexed.java): as Indexed, with displacements in BASE elements."""
         return cls._indexed("mpjx_type_hindexed", "Hindexed", array_of_blocklengths, array_of_displacements, oldtype)
 
+    @classmethod
+    def Struct(cls, array_of_blocklengths, array_of_displacements, array_of_types):
+        """Datatype.Struct (src/mpi/Struct.java): block i is blocklengths[i] items of types[i] starting
+        displacements[i] BASE elements from the origin; packed in the arrays' order. MPI.LB and MPI.UB set the
+        bounds (the reference's order-dependent rules: include/mpjx.h); all other components share one base type."""
+        bl, ds = [int(x) for x in array_of_blocklengths], [int(x) for x in array_of_displacements]
+        ts = list(array_of_types)
+        if not len(bl) == len(ds) == len(ts):
+            raise MPIException(f"Struct: {len(bl)} block lengths, {len(ds)} displacements and {len(ts)} types")
+        arr, codes = ctypes.c_int64 * max(len(bl), 1), ctypes.c_int * max(len(bl), 1)
+        code = ctypes.c_int()
+        _wrap("mpjx_type_struct", len(bl), arr(*bl), arr(*ds), codes(*[t.code for t in ts]), ctypes.byref(code))
+        data = [t for t in ts if not t.marker]
+        old = data[0] if data else MPI.BYTE
+        return cls._derived(code.value, old, f"Struct({bl}, {ds}, {[t.name for t in ts]})")
+
     def Commit(self):
         pass
 
@@ -131,7 +153,7 @@ class Datatype:
         return self.lb
 
     def Ub(self):
-        return self.lb + self.extent
+        return self.ub
 
     def __repr__(self):
         return f"MPI.{self.name}"
@@ -160,6 +182,9 @@ class MPI:
     LONG2 = Datatype(6, "LONG2", np.int64, "int64", 2)
     FLOAT2 = Datatype(7, "FLOAT2", np.float32, "float32", 2)
     DOUBLE2 = Datatype(8, "DOUBLE2", np.float64, "float64", 2)
+
+    LB = Datatype(10, "LB", np.int8, "int8", 0)  # the bound markers: components of Datatype.Struct only
+    UB = Datatype(11, "UB", np.int8, "int8", 0)
 
     MAX = Op(1, "MAX")
     MIN = Op(2, "MIN")
@@ -218,7 +243,7 @@ def _dev_ptr(buf, off, dt, need):
 def _dev_ptr_dt(buf, off, dt, count):
     """Device address of base element `off` for `count` items of the derived type dt: the buffer must hold
     the layout's true span ((count - 1) extents and one ub), not count * size elements."""
-    span = (count - 1) * dt.extent + dt.Ub() if count > 0 and dt.size > 0 else 0
+    span = (count - 1) * dt.extent + dt.true_ub if count > 0 and dt.size > 0 else 0
     if not buf.is_cuda:
         raise MPIException("torch tensor buffers must be on a GPU device")
     if not buf.is_contiguous():
@@ -511,7 +536,7 @@ class Intracomm:
         if len(c) < P or len(d) < P:
             raise MPIException(f"{name}: counts or displacements shorter than the communicator")
         arr = ctypes.c_int64 * P
-        span = max([dj + (cj - 1) * dt.extent + dt.Ub() for cj, dj in zip(c, d) if cj > 0 and dt.size > 0] or [0])
+        span = max([dj + (cj - 1) * dt.extent + dt.true_ub for cj, dj in zip(c, d) if cj > 0 and dt.size > 0] or [0])
         if span == 0 and buf is None:
             return None, arr(*c), arr(*d)
         if not buf.is_cuda:
@@ -627,6 +652,15 @@ class Intracomm:
         rp = _dev_ptr(recvbuf, recvoffset, recvtype, rspan)
         _wrap("mpjx_alltoallv", self._h, sp, sc, sd, rp, rc, rd, sendtype.code, None)
         self._sync_out()
+
+    MOVE_KERNEL_MOVES, MOVE_KERNEL_STRIDED, MOVE_KERNEL_INDEXED, MOVE_KERNEL_TRANSPOSE = 1, 2, 4, 8
+
+    def last_move_kernels(self):
+        """The kernels this rank's last data-movement call launched (mpjx_comm_last_move_kernels): an OR of
+        MOVE_KERNEL_*; 0 on a rank that launched nothing (rank 0 launches for a multicore world on one device)."""
+        m = ctypes.c_uint()
+        _wrap("mpjx_comm_last_move_kernels", self._h, ctypes.byref(m))
+        return m.value
 
     # -- Pack / Unpack / Pack_size (src/mpi/Comm.java:1860-1983): one mpjbuf section from, or into, items of any
     # datatype on a device tensor. The image (mpjbuf.Buffer there) is a torch.uint8 tensor on the device or in
