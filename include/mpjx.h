@@ -572,6 +572,82 @@ int mpjx_pack(mpjx_comm_t comm, const void *inbuf, int64_t count, int type, void
 int mpjx_unpack(mpjx_comm_t comm, const void *image, int64_t image_bytes, int64_t *position, void *outbuf,
                 int64_t count, int type, int *status, void *stream);
 
+/* ---- point-to-point: Send, Recv, Isend, Irecv, Sendrecv, Sendrecv_replace, Wait, Test, Waitall -------------------
+ * (src/mpi/Comm.java:381, :882, :1446, :1578, :2301, :2392; src/mpi/Request.java:81, :159; src/mpi/Status.java)
+ * One message from one rank to another, on device buffers, with any datatype on either side (the packed bytes
+ * of the send layout, in order, into the receive layout, as mpjx_alltoallv_dt moves them). count is in items of
+ * `type`; buf is the address of the first base element.
+ *
+ * Matching is MPI's, per world: a send (source, dest, tag) matches the first posted receive at dest, in post
+ * order, whose source is the sender or MPJX_ANY_SOURCE and whose tag is the send's or MPJX_ANY_TAG; a receive
+ * matches the first unmatched send likewise, so messages of one (source, dest) do not overtake. A send tag
+ * is >= 0. A MPJX_PROC_NULL peer completes at once: source MPJX_PROC_NULL, tag MPJX_ANY_TAG, 0 elements.
+ * Point-to-point and collective traffic never meet, and a sub-communicator matches apart from its parent.
+ *
+ * At match time both types must be made of the same basic type and the message's packed bytes must fit the
+ * receive layout (recvcount items). A shorter message is legal: the first n packed bytes of the receive layout
+ * are written and the rest keeps its contents. A base-type mismatch, an over-long message or a self-message whose
+ * two layouts share a byte completes BOTH requests with MPJX_ERR_ARG (mpjx_last_error names both envelopes);
+ * nothing is moved and the world stays usable. A receive type whose own blocks share a byte is MPJX_ERR_ARG at
+ * post. Argument errors found before posting (a bad rank, a negative count or tag, NULL with a nonzero count, an
+ * unknown or freed type) post nothing and do not fail the world.
+ *
+ * Nothing is launched at post time. A call that waits (mpjx_wait, mpjx_waitall, mpjx_test and the blocking
+ * calls) claims EVERY matched, unclaimed message its rank is a party to, sender or receiver, moves the whole
+ * batch on the communicator's stream — one k_msgs launch per table_max messages (mpjx_comm_p2p_stats), whatever their
+ * layouts; element transposes go to k_transpose — and the other party's wait then orders its stream after that
+ * batch. Either party can move a matched message, so no legal order of waits deadlocks. mpjx_wait and
+ * mpjx_waitall return once the data is complete on the host's view; mpjx_test never blocks. A wait on an
+ * unmatched request sleeps on the host and enqueues nothing on the GPU.
+ *
+ * Every host wait is bounded: MPJX_P2P_TIMEOUT_S seconds (default 300, read once when the world is created),
+ * or mpjx_comm_set_p2p_timeout for this rank. On expiry the call returns MPJX_ERR_INTERNAL naming the
+ * unmatched envelope and the world is marked failed: every peer's wait and later call errors out.
+ *
+ * mpjx_send of at most MPJX_P2P_EAGER_KIB packed KiB (default 128, the reference's protocol switch limit,
+ * src/runtime/starter/MPJRun.java:76; read once per world) is eager: the message is packed into a per-rank device
+ * slab of MPJX_P2P_EAGER_POOL_MIB MiB (default 8, src/mpjbuf/BufferConstants.java:28) on the rank's stream, posted
+ * as a contiguous message of the base type, and the call returns. With no room in the slab, or above the limit,
+ * mpjx_send is mpjx_isend + mpjx_wait. mpjx_isend never copies: the buffer is the caller's until the wait, as in
+ * MPI (the reference packs at Isend). MPJX_P2P_BATCH=0 (read once per world) moves a batch with one launch per
+ * kernel family instead of k_msgs: a comparison switch.
+ *
+ * Provided for multicore worlds (mpjx_comm_init_smp, _smp_rank) whose ranks address each other's memory, P = 1
+ * included; RCCL, IPC and other worlds return MPJX_ERR_UNSUPPORTED. Not provided: Probe, Bsend /
+ * Ssend / Rsend, persistent requests, Waitany / Waitsome / Test*all, Cancel, host arrays, big-endian and faithful
+ * modes, MPI.PACKED / OBJECT.
+ *
+ * mpjx_status.elements is the received base elements (for a receive type of size 0: the receive count);
+ * mpjx_get_count follows Comm.java:1517-1531: *count = elements / size if that divides, else MPJX_UNDEFINED; for a
+ * type of size 0, *count = status->elements and *elements = MPJX_UNDEFINED. A request handle is set to NULL on
+ * completion or free. mpjx_comm_destroy fails the communicator's pending requests; it does not free under them.
+ * mpjx_comm_p2p_stats: for this rank since creation, the k_msgs plus k_transpose launches, the messages it
+ * moved, its sends that went eager, and the messages per k_msgs launch. */
+enum { MPJX_ANY_SOURCE = -2, MPJX_ANY_TAG = -2, MPJX_PROC_NULL = -3, MPJX_UNDEFINED = -1 }; /* MPI.java:132-136 */
+typedef struct mpjx_request *mpjx_request_t;
+typedef struct { int source, tag, error; int64_t elements, bytes; } mpjx_status;
+
+int mpjx_isend(mpjx_comm_t comm, const void *buf, int64_t count, int type, int dest, int tag,
+               mpjx_request_t *request);
+int mpjx_irecv(mpjx_comm_t comm, void *buf, int64_t count, int type, int source, int tag,
+               mpjx_request_t *request);
+int mpjx_send(mpjx_comm_t comm, const void *buf, int64_t count, int type, int dest, int tag);
+int mpjx_recv(mpjx_comm_t comm, void *buf, int64_t count, int type, int source, int tag,
+              mpjx_status *status);
+int mpjx_sendrecv(mpjx_comm_t comm, const void *sendbuf, int64_t sendcount, int sendtype, int dest,
+                  int sendtag, void *recvbuf, int64_t recvcount, int recvtype, int source,
+                  int recvtag, mpjx_status *status);
+int mpjx_sendrecv_replace(mpjx_comm_t comm, void *buf, int64_t count, int type, int dest,
+                          int sendtag, int source, int recvtag, mpjx_status *status);
+int mpjx_wait(mpjx_request_t *request, mpjx_status *status);
+int mpjx_test(mpjx_request_t *request, int *flag, mpjx_status *status);
+int mpjx_waitall(int n, mpjx_request_t *requests, mpjx_status *statuses);
+int mpjx_request_free(mpjx_request_t *request);
+int mpjx_get_count(const mpjx_status *status, int type, int64_t *count, int64_t *elements);
+int mpjx_comm_set_p2p_timeout(mpjx_comm_t comm, double seconds);
+int mpjx_comm_p2p_stats(mpjx_comm_t comm, int64_t *launches, int64_t *moved, int64_t *eager,
+                        int *table_max);
+
 /* ---- host-resident variants (Java heap arrays / mpjbuf payloads) ---------------------------------
  * Synchronous. Buffers are ordinary host memory; the library stages them through device memory.
  * These are what the JNI shim calls with GetPrimitiveArrayCritical / GetDirectBufferAddress

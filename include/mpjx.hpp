@@ -158,6 +158,76 @@ struct MPI {
       BOR{MPJX_BOR, "BOR"}, LXOR{MPJX_LXOR, "LXOR"}, BXOR{MPJX_BXOR, "BXOR"}, MAXLOC{MPJX_MAXLOC, "MAXLOC"},
       MINLOC{MPJX_MINLOC, "MINLOC"};
   static inline bool isOldSelected = false;
+  static constexpr int ANY_SOURCE = MPJX_ANY_SOURCE, ANY_TAG = MPJX_ANY_TAG, PROC_NULL = MPJX_PROC_NULL,
+                       UNDEFINED = MPJX_UNDEFINED;  // src/mpi/MPI.java:132-136
+};
+
+// mpi.Status (src/mpi/Status.java): source and tag of the matched message, and its length
+struct Status {
+  int source = MPJX_PROC_NULL, tag = MPJX_ANY_TAG;
+  mpjx_status st{MPJX_PROC_NULL, MPJX_ANY_TAG, 0, 0, 0};
+  Status() = default;
+  explicit Status(const mpjx_status& s) : source(s.source), tag(s.tag), st(s) {}
+  int Get_count(const Datatype& dt) const {
+    int64_t c = 0;
+    check(mpjx_get_count(&st, dt.code, &c, nullptr), "Get_count");
+    return (int)c;
+  }
+  int Get_elements(const Datatype& dt) const {
+    int64_t e = 0;
+    check(mpjx_get_count(&st, dt.code, nullptr, &e), "Get_elements");
+    return (int)e;
+  }
+};
+
+// mpi.Request (src/mpi/Request.java). The buffer belongs to the operation until Wait or a successful Test.
+class Request {
+ public:
+  Request() = default;
+  explicit Request(mpjx_request_t r) : r_(r) {}
+  Request(const Request&) = delete;
+  Request& operator=(const Request&) = delete;
+  Request(Request&& o) noexcept : r_(o.r_) { o.r_ = nullptr; }
+  Request& operator=(Request&& o) noexcept {
+    if (this != &o) {
+      Free();
+      r_ = o.r_;
+      o.r_ = nullptr;
+    }
+    return *this;
+  }
+  ~Request() { Free(); }
+  bool Is_null() const { return r_ == nullptr; }
+  Status Wait() {
+    mpjx_status st;
+    check(mpjx_wait(&r_, &st), "Wait");
+    return Status(st);
+  }
+  // true (and *status set) if the operation is complete; never blocks
+  bool Test(Status* status = nullptr) {
+    mpjx_status st;
+    int flag = 0;
+    check(mpjx_test(&r_, &flag, &st), "Test");
+    if (flag && status) *status = Status(st);
+    return flag != 0;
+  }
+  void Free() {
+    if (r_) mpjx_request_free(&r_);
+  }
+  static std::vector<Status> Waitall(std::vector<Request>& reqs) {
+    std::vector<mpjx_request_t> h;
+    for (Request& r : reqs) h.push_back(r.r_);
+    std::vector<mpjx_status> st(reqs.size() + 1);
+    const int rc = mpjx_waitall((int)h.size(), h.data(), st.data());
+    for (Request& r : reqs) r.r_ = nullptr;
+    check(rc, "Waitall");
+    std::vector<Status> out;
+    for (size_t i = 0; i < reqs.size(); i++) out.emplace_back(st[i]);
+    return out;
+  }
+
+ private:
+  mpjx_request_t r_ = nullptr;
 };
 
 // One rank's communicator (src/mpi/Intracomm.java). Not copyable; Free() or the destructor releases it.
@@ -186,6 +256,56 @@ class Intracomm {
     c_ = nullptr;
   }
   void Barrier() { check(mpjx_barrier(c_), "Barrier"); }
+
+  // ---- point-to-point on device-resident buffers (src/mpi/Comm.java:381-2460): counts in items of the datatype,
+  // offsets in base elements. Multicore worlds (include/mpjx.h).
+  template <class T>
+  Request Isend(const T* buf, int offset, int count, const Datatype& dt, int dest, int tag) {
+    size_ok<T>(dt);
+    mpjx_request_t r = nullptr;
+    check(mpjx_isend(c_, buf ? buf + offset : nullptr, count, dt.code, dest, tag, &r), "Isend");
+    return Request(r);
+  }
+  template <class T>
+  Request Irecv(T* buf, int offset, int count, const Datatype& dt, int source, int tag) {
+    size_ok<T>(dt);
+    mpjx_request_t r = nullptr;
+    check(mpjx_irecv(c_, buf ? buf + offset : nullptr, count, dt.code, source, tag, &r), "Irecv");
+    return Request(r);
+  }
+  template <class T>
+  void Send(const T* buf, int offset, int count, const Datatype& dt, int dest, int tag) {
+    size_ok<T>(dt);
+    check(mpjx_send(c_, buf ? buf + offset : nullptr, count, dt.code, dest, tag), "Send");
+  }
+  template <class T>
+  Status Recv(T* buf, int offset, int count, const Datatype& dt, int source, int tag) {
+    size_ok<T>(dt);
+    mpjx_status st;
+    check(mpjx_recv(c_, buf ? buf + offset : nullptr, count, dt.code, source, tag, &st), "Recv");
+    return Status(st);
+  }
+  template <class T>
+  Status Sendrecv(const T* sendbuf, int sendoffset, int sendcount, const Datatype& sendtype, int dest, int sendtag,
+                  T* recvbuf, int recvoffset, int recvcount, const Datatype& recvtype, int source, int recvtag) {
+    size_ok<T>(sendtype);
+    size_ok<T>(recvtype);
+    mpjx_status st;
+    check(mpjx_sendrecv(c_, sendbuf ? sendbuf + sendoffset : nullptr, sendcount, sendtype.code, dest, sendtag,
+                        recvbuf ? recvbuf + recvoffset : nullptr, recvcount, recvtype.code, source, recvtag, &st),
+          "Sendrecv");
+    return Status(st);
+  }
+  template <class T>
+  Status Sendrecv_replace(T* buf, int offset, int count, const Datatype& dt, int dest, int sendtag, int source,
+                          int recvtag) {
+    size_ok<T>(dt);
+    mpjx_status st;
+    check(mpjx_sendrecv_replace(c_, buf ? buf + offset : nullptr, count, dt.code, dest, sendtag, source, recvtag, &st),
+          "Sendrecv_replace");
+    return Status(st);
+  }
+  void SetP2PTimeout(double seconds) { check(mpjx_comm_set_p2p_timeout(c_, seconds), "mpjx_comm_set_p2p_timeout"); }
 
   // ---- device-resident buffers (blocking) ----
   template <class T>

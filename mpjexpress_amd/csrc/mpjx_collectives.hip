@@ -2621,3 +2621,47 @@ extern "C" int mpjx_reduce_scatter_host(mpjx_comm_t c, const void* sendbuf, void
                                         int type, int op, unsigned flags) {
   return ended(c, reduce_scatter_host_entry(c, sendbuf, recvbuf, recvcounts, type, op, flags));
 }
+
+// ---- what the point-to-point calls (mpjx_p2p.hip) share with the block moves -------------------------------------
+namespace mpjx {
+
+int p2p_idx_table(mpjx_comm* c, const SideBytes& x, hipStream_t s, const IdxEnt** out) { return idx_table(c, x, s, out); }
+
+bool p2p_transpose_on() { return transpose_on(); }
+
+// MPJX_P2P_BATCH=0: the batch through DtMoves::launch, one launch per kernel family per table, for comparison
+// with k_msgs. A message shorter than its receive layout never takes k_transpose, which walks the whole of X.
+int p2p_launch_families(mpjx_comm* c, hipStream_t s, const std::vector<std::pair<SideBytes, SideBytes>>& msgs) {
+  DtMoves mv;
+  std::string err;
+  for (const auto& m : msgs) {
+    const SideBytes &a = m.first, &b = m.second;
+    if (a.total() <= 0) continue;
+    if (a.contiguous() && b.contiguous()) {
+      mv.ml.add((void*)(uintptr_t)b.base, (const void*)(uintptr_t)a.base, a.total());
+    } else if (a.regular() && b.regular()) {
+      TransposeSeg ts;
+      StridedSeg sg;
+      if (a.total() == b.total() && transpose_on() && plan_transpose_seg(a, b, &ts)) {
+        mv.tp.push_back(ts);
+        continue;
+      }
+      const int rc = plan_strided_seg(a, b, &sg, &err);
+      if (rc != kTypeOk) return fail(rc, "%s", err.c_str());
+      mv.st.push_back(sg);
+    } else {
+      const IdxEnt *stab, *dtab;
+      CHK(idx_table(c, a, s, &stab));
+      CHK(idx_table(c, b, s, &dtab));
+      IndexedSeg sg;
+      const int rc = plan_indexed_seg(a, stab, b, dtab, &sg, &err);
+      if (rc != kTypeOk) return fail(rc, "%s", err.c_str());
+      mv.ix.push_back(sg);
+    }
+  }
+  c->move_kernels = 0;
+  HIPCHK(mv.launch(c, s));
+  return MPJX_SUCCESS;
+}
+
+}  // namespace mpjx

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "mpjx_kernels.hpp"
+#include "mpjx_p2p_plan.hpp"
 
 namespace mpjx {
 
@@ -161,6 +162,9 @@ struct SmpWorld {
   std::vector<char> synced;  // fence(): the rank's stream drained before the rendezvous (no done[] wait)
   int refs = 0;
   std::atomic<int> failed{0};  // a rank left a collective early: every barrier fails from now on
+  // The point-to-point mailbox (mpjx_p2p_plan.hpp): its own lock and condition variable, apart from mu / cv /
+  // gen, which stay the collectives'
+  std::shared_ptr<Mailbox> mail;
   int barrier();
   void abort();
 };
@@ -312,10 +316,23 @@ struct mpjx_comm {
     std::shared_ptr<const mpjx::IrrLayout> host;
   };
   std::unordered_map<int, IdxTable> idx_tables;
+  // Point-to-point (mpjx_p2p.hip): this rank's wait limit in seconds (< 0: the world's MPJX_P2P_TIMEOUT_S), its
+  // eager slab (device memory, allocated at the first eager send and freed with the communicator) and the
+  // counters of mpjx_comm_p2p_stats
+  double p2p_timeout_s = -1;
+  char* p2p_slab = nullptr;
+  mpjx::EagerSlab p2p_chunks;
+  int64_t p2p_launches = 0, p2p_moved = 0, p2p_eager = 0;
+  // false once the communicator is destroyed: what a request handle that outlives it looks at
+  std::shared_ptr<std::atomic<bool>> p2p_alive = std::make_shared<std::atomic<bool>>(true);
 };
 
 namespace mpjx {
 // Make *buf hold at least `need` bytes (grown geometrically, 2 MiB granules). The outgrown buffer is
 // retired (kept allocated until the communicator is destroyed) once `s` has drained its users.
 int grow_device(mpjx_comm* c, char** buf, size_t* cap, size_t need, hipStream_t s);
+// mpjx_comm_destroy's point-to-point part (mpjx_p2p.hip): the rank's pending requests fail, its slab is freed
+void p2p_comm_destroy(mpjx_comm* c);
+// A new multicore world's mailbox, its settings read from the environment once
+std::shared_ptr<Mailbox> p2p_make_mailbox(int P);
 }  // namespace mpjx

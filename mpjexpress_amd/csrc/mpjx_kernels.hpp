@@ -31,6 +31,7 @@
 #include "mpjx_moves_plan.hpp"
 #include "mpjx_ops.hpp"
 #include "mpjx_indexed_plan.hpp"
+#include "mpjx_msgs_plan.hpp"
 #include "mpjx_pack_plan.hpp"
 #include "mpjx_strided_plan.hpp"
 #include "mpjx_transpose_plan.hpp"
@@ -659,6 +660,11 @@ hipError_t launch_indexed(const std::vector<IndexedSeg>& segs, hipStream_t s);
 // The element transposes among them (mpjx_k_transpose.hip): segments planned by plan_transpose_seg; kTransposeMax
 // segments per launch.
 hipError_t launch_transpose(const std::vector<TransposeSeg>& segs, hipStream_t s);
+
+// A batch of matched point-to-point messages of mixed layout kinds (mpjx_k_msgs.hip): segments planned by
+// plan_msg_seg, irregular sides' device tables uploaded on `s` or earlier; kMsgsMax segments per launch, each
+// launch added to *launches.
+hipError_t launch_msgs(const std::vector<MsgSeg>& segs, hipStream_t s, int64_t* launches);
 
 // One mpjbuf section packed from (unpack: unpacked into) a buffer of any layout (mpjx_k_pack.hip): the descriptor
 // planned by plan_pack_seg, an irregular layout's device table uploaded on `s` or earlier. One launch.

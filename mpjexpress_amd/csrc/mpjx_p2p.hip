@@ -1,0 +1,587 @@
+// mpjx_p2p.hip — the point-to-point calls of libmpjx on device buffers: Send, Recv, Isend, Irecv, Sendrecv,
+// Sendrecv_replace, Wait, Test, Waitall (src/mpi/Comm.java:381, :882, :1446, :1578, :2301, :2392;
+// src/mpi/Request.java:81, :159; src/mpi/Status.java:81, :173), exported through the C ABI of include/mpjx.h.
+//
+// Matching is the Mailbox's (mpjx_p2p_plan.hpp, one per multicore world, apart from the collectives' barrier).
+// This file posts requests, and moves matched pairs:
+//   post      the layout of `count` items of the type (plan_side), the argument checks, a ready event on the
+//             communicator's stream unless it is idle (as SmpTransport::share), Mailbox::post. No launch.
+//   progress  every call that waits claims EVERY matched pair its rank is a party to, makes its stream wait on
+//             the peers' ready events, moves the batch — k_msgs (mpjx_k_msgs.hip), one launch per kMsgsMax
+//             messages of any layout kinds; element transposes through launch_transpose — records one
+//             completion event for the batch and marks the pairs LAUNCHED. The other party's wait orders its
+//             stream after that event. MPJX_P2P_BATCH=0 sends the batch through DtMoves::launch instead.
+//   wait      sleeps on the mailbox's condition variable while a request is unmatched (nothing is enqueued on
+//             the GPU for it), bounded by MPJX_P2P_TIMEOUT_S / mpjx_comm_set_p2p_timeout and by the world's
+//             `failed` flag; ends with Transport::wait on the stream, as MPJX_FLAG_BLOCKING does.
+// Supported worlds: multicore worlds whose ranks address each other's memory (SmpWorld::direct), P = 1
+// included. The several-device form has no machine to be run on and is unverified.
+#include "mpjx_internal.hpp"
+
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <chrono>
+#include <string>
+#include <utility>
+
+using namespace mpjx;
+
+namespace mpjx {
+int p2p_idx_table(mpjx_comm* c, const SideBytes& x, hipStream_t s, const IdxEnt** out);
+bool p2p_transpose_on();
+int p2p_launch_families(mpjx_comm* c, hipStream_t s, const std::vector<std::pair<SideBytes, SideBytes>>& msgs);
+}  // namespace mpjx
+
+struct mpjx_request {
+  std::shared_ptr<P2PReq> q;
+  mpjx_comm* c = nullptr;
+  std::shared_ptr<SmpWorld> w;                 // keeps the mailbox and the world's `failed` flag alive
+  std::shared_ptr<std::atomic<bool>> alive;    // false once the communicator is destroyed: c dangles
+};
+
+namespace {
+
+struct Ev {
+  hipEvent_t e = nullptr;
+  ~Ev() {
+    if (e) (void)hipEventDestroy(e);
+  }
+};
+
+int record_event(hipStream_t s, std::shared_ptr<void>* out) {
+  auto ev = std::make_shared<Ev>();
+  HIPCHK(hipEventCreateWithFlags(&ev->e, hipEventDisableTiming));
+  HIPCHK(hipEventRecord(ev->e, s));
+  *out = ev;
+  return MPJX_SUCCESS;
+}
+hipEvent_t event_of(const std::shared_ptr<void>& p) { return p ? static_cast<Ev*>(p.get())->e : nullptr; }
+
+double env_double(const char* name, double dflt) {
+  const char* e = getenv(name);
+  const double v = e ? atof(e) : 0;
+  return v > 0 ? v : dflt;
+}
+
+// The world of a point-to-point call: MPJX_ERR_UNSUPPORTED outside direct multicore worlds
+int p2p_world(mpjx_comm* c, SmpTransport** out, bool usable = true) {
+  COMM_ARG(c);
+  auto* t = dynamic_cast<SmpTransport*>(c->tr.get());
+  if (!t || !t->w->direct || !t->w->mail)
+    return fail(MPJX_ERR_UNSUPPORTED, "point-to-point calls are provided for multicore worlds whose ranks address each "
+                "other's memory, not for the %s engine", c->tr ? c->tr->name() : "?");
+  if (usable && t->w->failed.load(std::memory_order_acquire))
+    return fail(MPJX_ERR_INTERNAL, "multicore world: another rank failed; the communicator is unusable");
+  *out = t;
+  return MPJX_SUCCESS;
+}
+
+// The stream of the call, ordered after the previous call's (Call::begin of the collectives)
+int p2p_begin(mpjx_comm* c, hipStream_t* s) {
+  HIPCHK(hipSetDevice(c->device));
+  *s = c->stream;
+  if (c->last_stream && c->last_stream != *s) {
+    if (!c->last_recorded) HIPCHK(hipEventRecord(c->last_ev, c->last_stream));
+    HIPCHK(hipStreamWaitEvent(*s, c->last_ev, 0));
+  }
+  c->last_stream = *s;
+  c->last_recorded = false;
+  return MPJX_SUCCESS;
+}
+
+// The checks before posting and the request of `count` items of `type` at buf. Nothing is posted.
+int plan_req(mpjx_comm* c, bool send, const void* buf, int64_t count, int type, int peer, int tag,
+             std::shared_ptr<P2PReq>* out) {
+  const char* who = send ? "send" : "receive";
+  TypeForm f;
+  if (!type_form(type, &f)) return fail(MPJX_ERR_ARG, "%s: unknown or freed datatype code %d", who, type);
+  if (count < 0) return fail(MPJX_ERR_ARG, "%s: negative count %lld", who, (long long)count);
+  const bool wild = !send && peer == MPJX_ANY_SOURCE;
+  if (!(peer >= 0 && peer < c->size) && peer != MPJX_PROC_NULL && !wild)
+    return fail(MPJX_ERR_ARG, "%s: rank %d out of range (the communicator has %d)", who, peer, c->size);
+  if (tag < 0 && !(!send && tag == MPJX_ANY_TAG)) return fail(MPJX_ERR_ARG, "%s: tag %d is negative", who, tag);
+  if (!send && f.irr && f.irr->self_overlap)
+    return fail(MPJX_ERR_ARG, "receive: datatype %d has blocks that share a byte: it can be sent, not received into", type);
+  auto q = std::make_shared<P2PReq>();
+  std::string err;
+  if (!plan_side(f, (uint64_t)(uintptr_t)buf, count, 0, &q->lay, &err)) return fail(MPJX_ERR_ARG, "%s: %s", who, err.c_str());
+  q->send = send;
+  q->rank = c->rank;
+  q->peer = peer;
+  q->tag = tag;
+  q->base = f.base;
+  q->bsz = f.bsz;
+  q->bytes = q->lay.total();
+  q->count = count;
+  q->empty_type = f.size() == 0;
+  if (q->bytes > 0 && !buf) return fail(MPJX_ERR_ARG, "%s: NULL buffer with count %lld", who, (long long)count);
+  if (q->bytes > 0 && peer != MPJX_PROC_NULL) CHK(check_dev_ptr(buf, "buffer"));
+  if (!send && q->lay.items_may_overlap()) {
+    int a = 0, b = 0;
+    if (strided_overlap({}, {q->lay}, &a, &b) == kRecvOverlap)
+      return fail(MPJX_ERR_ARG, "receive: %lld items of datatype %d (extent %lld) share a byte: they can be sent, not "
+                  "received into", (long long)count, type, (long long)f.extent());
+  }
+  *out = q;
+  return MPJX_SUCCESS;
+}
+
+// Posts q: a ready event unless the stream is idle, then the mailbox
+int post(mpjx_comm* c, SmpTransport* t, hipStream_t s, const std::shared_ptr<P2PReq>& q) {
+  if (q->peer != MPJX_PROC_NULL && q->bytes > 0 && hipStreamQuery(s) != hipSuccess) {
+    (void)hipGetLastError();
+    CHK(record_event(s, &q->ready));
+  }
+  (void)c;
+  t->w->mail->post(q);
+  return MPJX_SUCCESS;
+}
+
+mpjx_request* handle_of(mpjx_comm* c, SmpTransport* t, const std::shared_ptr<P2PReq>& q) {
+  auto* h = new mpjx_request;
+  h->q = q;
+  h->c = c;
+  h->w = t->w;
+  h->alive = c->p2p_alive;
+  return h;
+}
+
+// The batch's segments onto `s`: the peers' ready events first
+int move_batch(mpjx_comm* c, SmpTransport* t, hipStream_t s, const std::vector<std::shared_ptr<P2PPair>>& batch) {
+  std::vector<MsgSeg> segs;
+  std::vector<TransposeSeg> tps;
+  std::vector<std::pair<SideBytes, SideBytes>> plain;
+  const bool batched = t->w->mail->batch;
+  const bool tr_on = p2p_transpose_on();
+  std::string err;
+  for (const auto& p : batch) {
+    if (p->s->bytes <= 0) continue;
+    for (const P2PReq* q : {p->s.get(), p->r.get()})
+      if (q->rank != c->rank && q->ready) HIPCHK(hipStreamWaitEvent(s, event_of(q->ready), 0));
+    const SideBytes &a = p->s->lay, &b = p->r->lay;
+    if (!batched) {
+      plain.emplace_back(a, b);
+      continue;
+    }
+    TransposeSeg ts;
+    if (!(a.contiguous() && b.contiguous()) && a.regular() && b.regular() && a.total() == b.total() && tr_on &&
+        plan_transpose_seg(a, b, &ts)) {
+      tps.push_back(ts);
+      continue;
+    }
+    const IdxEnt *stab, *dtab;
+    CHK(p2p_idx_table(c, a, s, &stab));
+    CHK(p2p_idx_table(c, b, s, &dtab));
+    MsgSeg m{};
+    const int rc = plan_msg_seg(a, stab, b, dtab, &m, &err);
+    if (rc != kTypeOk) return fail(rc, "%s", err.c_str());
+    segs.push_back(m);
+  }
+  if (!batched) return p2p_launch_families(c, s, plain);
+  hipError_t e = launch_msgs(segs, s, &c->p2p_launches);
+  if (e == hipSuccess && !tps.empty()) {
+    e = launch_transpose(tps, s);
+    c->p2p_launches += ((int64_t)tps.size() + kTransposeMax - 1) / kTransposeMax;
+  }
+  if (e == hipErrorNoBinaryForGpu || e == hipErrorInvalidDeviceFunction)
+    return fail(MPJX_ERR_NO_DEVICE, "no gfx950 kernel image for this device: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return fail(MPJX_ERR_HIP, "point-to-point launch: %s", hipGetErrorString(e));
+  return MPJX_SUCCESS;
+}
+
+// Claims and moves every matched pair this rank is a party to
+int progress(mpjx_comm* c, SmpTransport* t, hipStream_t s) {
+  std::vector<std::shared_ptr<P2PPair>> batch;
+  Mailbox& mb = *t->w->mail;
+  mb.claim(c->rank, &batch);
+  if (batch.empty()) return MPJX_SUCCESS;
+  std::shared_ptr<void> done;
+  int rc = move_batch(c, t, s, batch);
+  if (rc == MPJX_SUCCESS) rc = record_event(s, &done);
+  if (rc != MPJX_SUCCESS) {
+    mb.launched(batch, nullptr, rc, mpjx_last_error());
+    return rc;
+  }
+  c->p2p_moved += (int64_t)batch.size();
+  mb.launched(batch, done);
+  return MPJX_SUCCESS;
+}
+
+void fill(mpjx_status* out, const P2PStatus& st) {
+  if (!out) return;
+  out->source = st.source;
+  out->tag = st.tag;
+  out->error = st.error;
+  out->elements = st.elements;
+  out->bytes = st.bytes;
+}
+
+void drop(mpjx_request_t* r) {
+  mpjx_request* h = *r;
+  if (!h) return;
+  if (h->w && h->w->mail) {
+    h->w->mail->withdraw(h->q);
+    h->w->mail->release(h->q);
+  }
+  delete h;
+  *r = nullptr;
+}
+
+Mailbox::Clock::time_point deadline_of(mpjx_comm* c, SmpTransport* t) {
+  const double sec = c->p2p_timeout_s > 0 ? c->p2p_timeout_s : t->w->mail->timeout_s;
+  return Mailbox::Clock::now() + std::chrono::duration_cast<Mailbox::Clock::duration>(std::chrono::duration<double>(sec));
+}
+
+// Waits for n requests of one communicator (NULL handles are skipped). Every handle is NULL on return.
+int wait_many(int n, mpjx_request_t* reqs, mpjx_status* statuses) {
+  mpjx_comm* c = nullptr;
+  for (int i = 0; i < n; i++) {
+    if (statuses) fill(&statuses[i], P2PStatus{});
+    mpjx_request* h = reqs[i];
+    if (!h) continue;
+    if (!h->alive->load()) {
+      for (int j = 0; j < n; j++) drop(&reqs[j]);
+      return fail(MPJX_ERR_INTERNAL, "the request's communicator was destroyed while it was pending");
+    }
+    if (c && h->c != c) return fail(MPJX_ERR_ARG, "the requests of one wait must belong to one communicator");
+    c = h->c;
+  }
+  if (!c) return MPJX_SUCCESS;
+  SmpTransport* t = nullptr;
+  hipStream_t s = nullptr;
+  int rc = p2p_world(c, &t);
+  if (rc == MPJX_SUCCESS) rc = p2p_begin(c, &s);
+  if (rc != MPJX_SUCCESS) {
+    for (int j = 0; j < n; j++) drop(&reqs[j]);
+    return rc;
+  }
+  Mailbox& mb = *t->w->mail;
+  const auto deadline = deadline_of(c, t);
+  for (int i = 0; i < n && rc == MPJX_SUCCESS; i++) {
+    if (!reqs[i]) continue;
+    const std::shared_ptr<P2PReq>& q = reqs[i]->q;
+    for (;;) {
+      rc = progress(c, t, s);
+      if (rc != MPJX_SUCCESS) break;
+      const Mailbox::Wake w = mb.wait(q, deadline, &t->w->failed);
+      if (w == Mailbox::kWakeMatched) continue;
+      if (w == Mailbox::kWakeSettled) break;
+      const std::string env = q->envelope();
+      if (w == Mailbox::kWakeFailed)
+        rc = fail(MPJX_ERR_INTERNAL, "multicore world: another rank failed while %s was pending", env.c_str());
+      else
+        rc = fail(MPJX_ERR_INTERNAL, "point-to-point wait timed out: %s was not %s within the limit", env.c_str(),
+                  q->pair ? "moved by the rank that claimed it" : "matched");
+      break;
+    }
+  }
+  if (rc != MPJX_SUCCESS) {
+    const std::string msg = mpjx_last_error();
+    for (int j = 0; j < n; j++) drop(&reqs[j]);
+    c->tr->call_failed();  // every peer's wait and later call errors out: no rank hangs
+    mb.notify();
+    return fail(rc, "%s", msg.c_str());
+  }
+  // every request is settled: order the stream after the batches other ranks moved, then drain it
+  for (int i = 0; i < n; i++) {
+    if (!reqs[i]) continue;
+    const std::shared_ptr<P2PPair> p = reqs[i]->q->pair;
+    if (p && p->state == kPairLaunched && p->mover != c->rank && p->done) {
+      const hipError_t e = hipStreamWaitEvent(s, event_of(p->done), 0);
+      if (e != hipSuccess && rc == MPJX_SUCCESS) rc = fail(MPJX_ERR_HIP, "hipStreamWaitEvent: %s", hipGetErrorString(e));
+    }
+  }
+  if (rc == MPJX_SUCCESS) rc = c->tr->wait(s);
+  c->last_stream = nullptr;  // complete on the host's view: whatever comes next is ordered after it
+  c->last_recorded = false;
+  std::string first;
+  for (int i = 0; i < n; i++) {
+    if (!reqs[i]) continue;
+    const std::shared_ptr<P2PReq>& q = reqs[i]->q;
+    if (q->orphan && !q->pair && rc == MPJX_SUCCESS) {
+      rc = MPJX_ERR_INTERNAL;
+      first = "the request was withdrawn: " + q->envelope();
+    }
+    const P2PStatus st = p2p_status(*q);
+    if (statuses) fill(&statuses[i], st);
+    if (st.error != kP2POk && rc == MPJX_SUCCESS) {
+      rc = st.error;
+      first = q->pair->msg;
+    }
+    drop(&reqs[i]);
+  }
+  if (rc != MPJX_SUCCESS && !first.empty()) return fail(rc, "%s", first.c_str());
+  return rc;
+}
+
+SideBytes packed_side(const char* p, int64_t bytes) {
+  SideBytes x;
+  x.base = (uint64_t)(uintptr_t)p;
+  x.bb = x.sb = x.eb = bytes;
+  x.nb = x.items = 1;
+  return x;
+}
+
+// Packs q's layout to `at` on s and makes q a contiguous message from there
+int pack_to(mpjx_comm* c, SmpTransport* t, hipStream_t s, const std::shared_ptr<P2PReq>& q, char* at) {
+  auto tmp = std::make_shared<P2PPair>();
+  tmp->s = q;
+  tmp->r = std::make_shared<P2PReq>(*q);
+  tmp->r->lay = packed_side(at, q->bytes);
+  tmp->r->ready.reset();
+  CHK(move_batch(c, t, s, {tmp}));
+  q->lay = tmp->r->lay;
+  return MPJX_SUCCESS;
+}
+
+// True once the eager message of q needs its chunk no longer (called under the mailbox lock)
+bool chunk_done(const std::shared_ptr<P2PReq>& q) {
+  bool done = q->consumed || q->orphan;
+  if (!done && q->pair) {
+    const P2PPair& p = *q->pair;
+    done = p.state == kPairFailed || (p.state == kPairLaunched && (!p.done || hipEventQuery(event_of(p.done)) == hipSuccess));
+    (void)hipGetLastError();
+  }
+  if (done) q->pair.reset();
+  return done;
+}
+
+int isend_impl(mpjx_comm* c, const void* buf, int64_t count, int type, int dest, int tag, mpjx_request_t* request,
+               bool eager_ok, bool* went_eager) {
+  SmpTransport* t = nullptr;
+  CHK(p2p_world(c, &t));
+  std::shared_ptr<P2PReq> q;
+  CHK(plan_req(c, true, buf, count, type, dest, tag, &q));
+  hipStream_t s = nullptr;
+  CHK(p2p_begin(c, &s));
+  Mailbox& mb = *t->w->mail;
+  if (went_eager) *went_eager = false;
+  if (eager_ok && dest != MPJX_PROC_NULL && q->bytes <= mb.eager_bytes) {
+    int64_t off = 0;
+    if (q->bytes > 0) {
+      if (!c->p2p_slab) {
+        HIPCHK(hipMalloc((void**)&c->p2p_slab, (size_t)mb.pool_bytes));
+        c->p2p_chunks = EagerSlab(mb.pool_bytes);
+      }
+      std::lock_guard<std::mutex> g(mb.mutex());
+      off = c->p2p_chunks.alloc(q->bytes, q, chunk_done);
+    }
+    if (off >= 0) {
+      q->eager = true;
+      if (q->bytes > 0) CHK(pack_to(c, t, s, q, c->p2p_slab + off));
+      CHK(post(c, t, s, q));
+      c->p2p_eager++;
+      if (went_eager) *went_eager = true;
+      return MPJX_SUCCESS;
+    }
+  }
+  CHK(post(c, t, s, q));
+  *request = handle_of(c, t, q);
+  return MPJX_SUCCESS;
+}
+
+int irecv_impl(mpjx_comm* c, void* buf, int64_t count, int type, int source, int tag, mpjx_request_t* request) {
+  SmpTransport* t = nullptr;
+  CHK(p2p_world(c, &t));
+  std::shared_ptr<P2PReq> q;
+  CHK(plan_req(c, false, buf, count, type, source, tag, &q));
+  hipStream_t s = nullptr;
+  CHK(p2p_begin(c, &s));
+  CHK(post(c, t, s, q));
+  *request = handle_of(c, t, q);
+  return MPJX_SUCCESS;
+}
+
+}  // namespace
+
+namespace mpjx {
+
+std::shared_ptr<Mailbox> p2p_make_mailbox(int P) {
+  auto mb = std::make_shared<Mailbox>(P);
+  mb->timeout_s = env_double("MPJX_P2P_TIMEOUT_S", 300);
+  mb->eager_bytes = (int64_t)(env_double("MPJX_P2P_EAGER_KIB", 128) * 1024);
+  mb->pool_bytes = (int64_t)env_double("MPJX_P2P_EAGER_POOL_MIB", 8) << 20;
+  const char* e = getenv("MPJX_P2P_BATCH");
+  mb->batch = !(e && e[0] == '0' && e[1] == 0);
+  return mb;
+}
+
+void p2p_comm_destroy(mpjx_comm* c) {
+  c->p2p_alive->store(false);
+  auto* t = dynamic_cast<SmpTransport*>(c->tr.get());
+  if (t && t->w->mail) {
+    t->w->mail->retire_rank(c->rank);
+    std::lock_guard<std::mutex> g(t->w->mail->mutex());
+    c->p2p_chunks.clear([](const std::shared_ptr<P2PReq>& q) { q->pair.reset(); });
+  }
+  if (c->p2p_slab) (void)hipFree(c->p2p_slab);
+  c->p2p_slab = nullptr;
+}
+
+}  // namespace mpjx
+
+extern "C" int mpjx_isend(mpjx_comm_t c, const void* buf, int64_t count, int type, int dest, int tag,
+                          mpjx_request_t* request) {
+  COMM_ARG(c);
+  if (!request) return fail(MPJX_ERR_ARG, "request is NULL");
+  *request = nullptr;
+  return isend_impl(c, buf, count, type, dest, tag, request, false, nullptr);
+}
+
+extern "C" int mpjx_irecv(mpjx_comm_t c, void* buf, int64_t count, int type, int source, int tag,
+                          mpjx_request_t* request) {
+  COMM_ARG(c);
+  if (!request) return fail(MPJX_ERR_ARG, "request is NULL");
+  *request = nullptr;
+  return irecv_impl(c, buf, count, type, source, tag, request);
+}
+
+extern "C" int mpjx_send(mpjx_comm_t c, const void* buf, int64_t count, int type, int dest, int tag) {
+  COMM_ARG(c);
+  mpjx_request_t r = nullptr;
+  bool eager = false;
+  CHK(isend_impl(c, buf, count, type, dest, tag, &r, true, &eager));
+  return eager ? MPJX_SUCCESS : wait_many(1, &r, nullptr);
+}
+
+extern "C" int mpjx_recv(mpjx_comm_t c, void* buf, int64_t count, int type, int source, int tag, mpjx_status* status) {
+  COMM_ARG(c);
+  mpjx_request_t r = nullptr;
+  CHK(irecv_impl(c, buf, count, type, source, tag, &r));
+  return wait_many(1, &r, status);
+}
+
+extern "C" int mpjx_sendrecv(mpjx_comm_t c, const void* sendbuf, int64_t sendcount, int sendtype, int dest, int sendtag,
+                             void* recvbuf, int64_t recvcount, int recvtype, int source, int recvtag,
+                             mpjx_status* status) {
+  COMM_ARG(c);
+  // Comm.java:2334-2343: Irecv, Isend, wait for both. Both are checked before either is posted.
+  SmpTransport* t = nullptr;
+  CHK(p2p_world(c, &t));
+  std::shared_ptr<P2PReq> probe;
+  CHK(plan_req(c, true, sendbuf, sendcount, sendtype, dest, sendtag, &probe));
+  mpjx_request_t r[2] = {nullptr, nullptr};
+  CHK(irecv_impl(c, recvbuf, recvcount, recvtype, source, recvtag, &r[0]));
+  const int rc = isend_impl(c, sendbuf, sendcount, sendtype, dest, sendtag, &r[1], false, nullptr);
+  if (rc != MPJX_SUCCESS) {
+    drop(&r[0]);
+    return rc;
+  }
+  mpjx_status st[2];
+  const int wrc = wait_many(2, r, st);
+  if (status) *status = st[0];
+  return wrc;
+}
+
+extern "C" int mpjx_sendrecv_replace(mpjx_comm_t c, void* buf, int64_t count, int type, int dest, int sendtag,
+                                     int source, int recvtag, mpjx_status* status) {
+  COMM_ARG(c);
+  SmpTransport* t = nullptr;
+  CHK(p2p_world(c, &t));
+  std::shared_ptr<P2PReq> sq, rq;
+  CHK(plan_req(c, true, buf, count, type, dest, sendtag, &sq));
+  CHK(plan_req(c, false, buf, count, type, source, recvtag, &rq));
+  hipStream_t s = nullptr;
+  CHK(p2p_begin(c, &s));
+  // the outgoing message leaves from the communicator's staging, so the incoming one may land in buf
+  if (sq->bytes > 0 && dest != MPJX_PROC_NULL) {
+    CHK(grow_device(c, &c->dtstage, &c->dtstage_bytes, (size_t)sq->bytes, s));
+    CHK(pack_to(c, t, s, sq, c->dtstage));
+  }
+  CHK(post(c, t, s, rq));
+  mpjx_request_t r[2] = {handle_of(c, t, rq), nullptr};
+  const int rc = post(c, t, s, sq);
+  if (rc != MPJX_SUCCESS) {
+    drop(&r[0]);
+    return rc;
+  }
+  r[1] = handle_of(c, t, sq);
+  mpjx_status st[2];
+  const int wrc = wait_many(2, r, st);
+  if (status) *status = st[0];
+  return wrc;
+}
+
+extern "C" int mpjx_wait(mpjx_request_t* request, mpjx_status* status) {
+  if (!request) return fail(MPJX_ERR_ARG, "request is NULL");
+  return wait_many(1, request, status);
+}
+
+extern "C" int mpjx_waitall(int n, mpjx_request_t* requests, mpjx_status* statuses) {
+  if (n < 0 || (n > 0 && !requests)) return fail(MPJX_ERR_ARG, "bad request list (n = %d)", n);
+  return wait_many(n, requests, statuses);
+}
+
+extern "C" int mpjx_test(mpjx_request_t* request, int* flag, mpjx_status* status) {
+  if (!request || !flag) return fail(MPJX_ERR_ARG, "NULL argument");
+  *flag = 0;
+  fill(status, P2PStatus{});
+  mpjx_request* h = *request;
+  if (!h) {
+    *flag = 1;
+    return MPJX_SUCCESS;
+  }
+  if (!h->alive->load()) {
+    drop(request);
+    return fail(MPJX_ERR_INTERNAL, "the request's communicator was destroyed while it was pending");
+  }
+  mpjx_comm* c = h->c;
+  SmpTransport* t = nullptr;
+  hipStream_t s = nullptr;
+  CHK(p2p_world(c, &t));
+  CHK(p2p_begin(c, &s));
+  CHK(progress(c, t, s));
+  if (!t->w->mail->settled(h->q)) return MPJX_SUCCESS;
+  const std::shared_ptr<P2PPair> p = h->q->pair;
+  if (p && p->state == kPairLaunched && p->done) {
+    const hipError_t e = hipEventQuery(event_of(p->done));
+    if (e == hipErrorNotReady) {
+      (void)hipGetLastError();
+      return MPJX_SUCCESS;
+    }
+    if (e != hipSuccess) return fail(MPJX_ERR_HIP, "hipEventQuery: %s", hipGetErrorString(e));
+  }
+  const P2PStatus st = p2p_status(*h->q);
+  const std::string msg = p ? p->msg : std::string();
+  fill(status, st);
+  *flag = 1;
+  drop(request);
+  return st.error == kP2POk ? MPJX_SUCCESS : fail(st.error, "%s", msg.c_str());
+}
+
+extern "C" int mpjx_request_free(mpjx_request_t* request) {
+  if (!request) return fail(MPJX_ERR_ARG, "request is NULL");
+  drop(request);
+  return MPJX_SUCCESS;
+}
+
+extern "C" int mpjx_get_count(const mpjx_status* status, int type, int64_t* count, int64_t* elements) {
+  if (!status) return fail(MPJX_ERR_ARG, "status is NULL");
+  TypeForm f;
+  if (!type_form(type, &f)) return fail(MPJX_ERR_ARG, "mpjx_get_count: unknown or freed datatype code %d", type);
+  int64_t cn = 0, el = 0;
+  p2p_get_count(status->elements, f.size(), &cn, &el);
+  if (count) *count = cn;
+  if (elements) *elements = el;
+  return MPJX_SUCCESS;
+}
+
+extern "C" int mpjx_comm_set_p2p_timeout(mpjx_comm_t c, double seconds) {
+  SmpTransport* t = nullptr;
+  CHK(p2p_world(c, &t, false));
+  if (!(seconds > 0)) return fail(MPJX_ERR_ARG, "the timeout must be positive (%g)", seconds);
+  c->p2p_timeout_s = seconds;
+  return MPJX_SUCCESS;
+}
+
+extern "C" int mpjx_comm_p2p_stats(mpjx_comm_t c, int64_t* launches, int64_t* moved, int64_t* eager, int* table_max) {
+  SmpTransport* t = nullptr;
+  CHK(p2p_world(c, &t, false));
+  if (launches) *launches = c->p2p_launches;
+  if (moved) *moved = c->p2p_moved;
+  if (eager) *eager = c->p2p_eager;
+  if (table_max) *table_max = kMsgsMax;
+  return MPJX_SUCCESS;
+}

@@ -1,0 +1,364 @@
+// mpjx_p2p_plan.hpp — the matching engine of the point-to-point calls (Send, Recv, Isend, Irecv, Sendrecv,
+// Waitall: src/mpi/Comm.java:381-2460, src/mpi/Request.java) and the first-fit allocator of the eager slab. No
+// HIP include: plain C++17, compiled, tested and sanitized on the CPU (tests/cpp/p2p_match_test.cpp); the
+// library's entry points (mpjx_p2p.hip) drive exactly this code.
+//
+// One Mailbox per multicore world, with its own mutex and condition variable: point-to-point and collective
+// traffic never meet (the reference's two contexts), and a sub-communicator, being a world of its own, has a
+// mailbox of its own. Per destination rank the mailbox keeps two lists in post order: posted receives and
+// unmatched sends. The matching rule is MPI's: a send (src, dst, tag) matches the first posted receive at dst
+// whose source is src or ANY_SOURCE and whose tag is tag or ANY_TAG; a receive matches the first unmatched
+// send likewise. Both lists are walked front to back, which gives non-overtaking per (src, dst).
+//
+// A matched pair goes MATCHED -> CLAIMED -> LAUNCHED. Nothing is launched at post time: a call that waits
+// claims EVERY matched, unclaimed pair its rank is a party to (claim), moves the batch on its own stream and
+// marks it LAUNCHED with the batch's completion event (launched). Either party may move a pair, so no legal
+// order of waits deadlocks. A pair that fails its checks at match time (base types differ, the message is
+// longer than the receive layout, a self-message whose layouts share a byte) is FAILED at once on both
+// requests; nothing moves and the world stays usable.
+#pragma once
+#include <stdint.h>
+
+#include <atomic>
+#include <chrono>
+#include <condition_variable>
+#include <deque>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "mpjx_strided_plan.hpp"
+
+namespace mpjx {
+
+constexpr int kAnySource = -2, kAnyTag = -2, kProcNull = -3;  // src/mpi/MPI.java:132-136
+constexpr int kUndefined = -1;
+constexpr int kP2POk = 0, kP2PErrArg = -1, kP2PErrInternal = -7;  // MPJX_SUCCESS / _ERR_ARG / _ERR_INTERNAL
+
+enum PairState { kPairMatched = 0, kPairClaimed = 1, kPairLaunched = 2, kPairFailed = 3 };
+
+struct P2PPair;
+
+// One posted send or receive. `peer` is the destination of a send and the source (or ANY_SOURCE) asked for
+// by a receive; `lay` the layout in bytes (absolute addresses), `bytes` its packed bytes: the message's
+// length for a send, the room for a receive.
+struct P2PReq {
+  bool send = false;
+  int rank = 0, peer = 0, tag = 0;
+  int base = 0, bsz = 1;
+  int64_t bytes = 0;
+  int64_t count = 0;   // the receive count (items), for the status of a receive whose type has size 0
+  bool empty_type = false;
+  SideBytes lay;
+  std::shared_ptr<void> ready;  // the poster's ready event, or none when its stream was idle at post
+  std::shared_ptr<P2PPair> pair;
+  bool null_peer = false;  // PROC_NULL: complete at once
+  bool orphan = false;     // its communicator was destroyed, or its wait gave up: no longer in any list
+  bool eager = false;      // an eager send: its message lies in the sender's slab and nobody waits for it
+  bool consumed = false;   // eager: the receiver has completed its wait, the slab chunk may be reused
+  std::string envelope() const {
+    return std::string(send ? "send" : "recv") + "(rank " + std::to_string(rank) + (send ? " -> " : " <- ") +
+           (peer == kAnySource ? std::string("ANY_SOURCE") : std::to_string(peer)) + ", tag " +
+           (tag == kAnyTag ? std::string("ANY_TAG") : std::to_string(tag)) + ", " + std::to_string(bytes) + " B)";
+  }
+};
+
+struct P2PPair {
+  std::shared_ptr<P2PReq> s, r;
+  int state = kPairMatched;
+  int mover = -1;               // the rank that claimed it
+  std::shared_ptr<void> done;   // the completion event of the batch that moved it (kept alive by the pair)
+  int err = kP2POk;
+  std::string msg;
+};
+
+// What a completed request reports (mpjx_status)
+struct P2PStatus {
+  int source = kProcNull, tag = kAnyTag, error = kP2POk;
+  int64_t elements = 0, bytes = 0;
+};
+
+inline P2PStatus p2p_status(const P2PReq& q) {
+  P2PStatus st;
+  if (q.null_peer || !q.pair) return st;
+  const P2PPair& p = *q.pair;
+  st.error = p.err;
+  st.source = p.s->rank;
+  st.tag = p.s->tag;
+  if (p.err != kP2POk) return st;
+  st.bytes = p.s->bytes;
+  st.elements = p.s->bytes / (q.bsz > 0 ? q.bsz : 1);
+  if (!q.send && q.empty_type) st.elements = q.count;  // Comm.java:1526-1531: a type of size 0 reports the count
+  return st;
+}
+
+// count and elements of `st` for a type of `size` base elements per item (Comm.java:1517-1531)
+inline void p2p_get_count(int64_t st_elements, int64_t size, int64_t* count, int64_t* elements) {
+  if (size != 0) {
+    *elements = st_elements;
+    *count = st_elements % size == 0 ? st_elements / size : kUndefined;
+  } else {
+    *count = st_elements;
+    *elements = kUndefined;
+  }
+}
+
+class Mailbox {
+ public:
+  using Clock = std::chrono::steady_clock;
+  explicit Mailbox(int P) : recvs_((size_t)P), sends_((size_t)P), P_(P) {}
+  int size() const { return P_; }
+
+  // Read once at world creation (mpjx_p2p.hip): MPJX_P2P_TIMEOUT_S, MPJX_P2P_EAGER_KIB, MPJX_P2P_EAGER_POOL_MIB,
+  // MPJX_P2P_BATCH
+  double timeout_s = 300;
+  int64_t eager_bytes = (int64_t)128 << 10;
+  int64_t pool_bytes = (int64_t)8 << 20;
+  bool batch = true;
+
+  // Posts q (send: to q->peer; receive: at q->rank) and matches it if a partner waits. A PROC_NULL peer
+  // completes at once. Returns the pair when one was made (FAILED pairs included).
+  std::shared_ptr<P2PPair> post(const std::shared_ptr<P2PReq>& q) {
+    std::shared_ptr<P2PPair> made;
+    {
+      std::lock_guard<std::mutex> g(mu_);
+      if (q->peer == kProcNull) {
+        q->null_peer = true;
+        return nullptr;
+      }
+      const int dst = q->send ? q->peer : q->rank;
+      auto& mine = q->send ? sends_[(size_t)dst] : recvs_[(size_t)dst];
+      auto& other = q->send ? recvs_[(size_t)dst] : sends_[(size_t)dst];
+      for (auto it = other.begin(); it != other.end(); ++it) {
+        const P2PReq& s = q->send ? *q : **it;
+        const P2PReq& r = q->send ? **it : *q;
+        if ((r.peer == kAnySource || r.peer == s.rank) && (r.tag == kAnyTag || r.tag == s.tag)) {
+          made = std::make_shared<P2PPair>();
+          made->s = q->send ? q : *it;
+          made->r = q->send ? *it : q;
+          other.erase(it);
+          break;
+        }
+      }
+      if (!made) {
+        mine.push_back(q);
+        return nullptr;
+      }
+      made->s->pair = made;
+      made->r->pair = made;
+      if (check(*made)) matched_.push_back(made);
+    }
+    cv_.notify_all();
+    return made;
+  }
+
+  // Every MATCHED pair `rank` is a party to becomes CLAIMED by it, in match order per list walk
+  void claim(int rank, std::vector<std::shared_ptr<P2PPair>>* out) {
+    out->clear();
+    std::lock_guard<std::mutex> g(mu_);
+    for (auto it = matched_.begin(); it != matched_.end();) {
+      P2PPair& p = **it;
+      if (p.state == kPairMatched && (p.s->rank == rank || p.r->rank == rank)) {
+        p.state = kPairClaimed;
+        p.mover = rank;
+        out->push_back(*it);
+        it = matched_.erase(it);
+      } else {
+        ++it;
+      }
+    }
+  }
+
+  // The batch was enqueued (err == kP2POk: `done` is its completion event) or could not be
+  void launched(const std::vector<std::shared_ptr<P2PPair>>& batch, const std::shared_ptr<void>& done, int err = kP2POk,
+                const std::string& msg = std::string()) {
+    {
+      std::lock_guard<std::mutex> g(mu_);
+      for (const auto& p : batch) {
+        p->done = done;
+        p->err = err;
+        p->msg = msg;
+        p->state = err == kP2POk ? kPairLaunched : kPairFailed;
+      }
+    }
+    cv_.notify_all();
+  }
+
+  enum Wake { kWakeSettled, kWakeMatched, kWakeTimeout, kWakeFailed };
+  // Sleeps until q is LAUNCHED or FAILED (settled), or MATCHED and unclaimed (the caller claims it), until
+  // `deadline`, or until *failed (the world's flag, observed at least every 50 ms) is set.
+  Wake wait(const std::shared_ptr<P2PReq>& q, Clock::time_point deadline, const std::atomic<int>* failed) {
+    std::unique_lock<std::mutex> lk(mu_);
+    for (;;) {
+      if (q->null_peer || q->orphan) return kWakeSettled;
+      if (q->pair) {
+        const int st = q->pair->state;
+        if (st == kPairLaunched || st == kPairFailed) return kWakeSettled;
+        if (st == kPairMatched) return kWakeMatched;
+      }
+      if (failed && failed->load(std::memory_order_acquire)) return kWakeFailed;
+      const auto now = Clock::now();
+      if (now >= deadline) return kWakeTimeout;
+      const auto slice = std::min<Clock::duration>(deadline - now, std::chrono::milliseconds(50));
+      // a slice on the system clock (pthread_cond_timedwait, which ThreadSanitizer intercepts); the deadline itself
+      // is on the steady clock
+      cv_.wait_until(lk, std::chrono::system_clock::now() + slice);
+    }
+  }
+
+  // The state of q for a call that does not sleep
+  bool settled(const std::shared_ptr<P2PReq>& q) {
+    std::lock_guard<std::mutex> g(mu_);
+    if (q->null_peer || q->orphan) return true;
+    return q->pair && (q->pair->state == kPairLaunched || q->pair->state == kPairFailed);
+  }
+
+  // q leaves the lists unmatched (its wait gave up, or mpjx_request_free); false if it was matched already
+  bool withdraw(const std::shared_ptr<P2PReq>& q) {
+    std::lock_guard<std::mutex> g(mu_);
+    if (q->pair || q->null_peer) return false;
+    q->orphan = true;
+    for (auto* lists : {&recvs_, &sends_})
+      for (auto& l : *lists)
+        for (auto it = l.begin(); it != l.end(); ++it)
+          if (it->get() == q.get()) {
+            l.erase(it);
+            return true;
+          }
+    return true;
+  }
+
+  // The communicator of `rank` is destroyed: its unmatched requests leave the lists and its unmoved pairs
+  // fail on both sides (nothing is moved into or out of memory the caller is about to free)
+  void retire_rank(int rank) {
+    {
+      std::lock_guard<std::mutex> g(mu_);
+      for (auto* lists : {&recvs_, &sends_})
+        for (auto& l : *lists)
+          for (auto it = l.begin(); it != l.end();)
+            if ((*it)->rank == rank) {
+              (*it)->orphan = true;
+              it = l.erase(it);
+            } else {
+              ++it;
+            }
+      for (auto it = matched_.begin(); it != matched_.end();) {
+        P2PPair& p = **it;
+        if (p.s->rank == rank || p.r->rank == rank) {
+          p.state = kPairFailed;
+          p.err = kP2PErrInternal;
+          p.msg = "the communicator of rank " + std::to_string(rank) + " was destroyed with " + p.s->envelope() +
+                  " matched to " + p.r->envelope() + " still pending";
+          it = matched_.erase(it);
+        } else {
+          ++it;
+        }
+      }
+    }
+    cv_.notify_all();
+  }
+
+  // The caller is done with q (its status was read, or it is freed): q lets go of its pair. A pair and its two
+  // requests refer to each other, so the pair lives until both requests have been released.
+  void release(const std::shared_ptr<P2PReq>& q) {
+    std::shared_ptr<P2PPair> drop;
+    std::lock_guard<std::mutex> g(mu_);
+    drop.swap(q->pair);
+    if (drop && !q->send && drop->s->eager) {  // nobody else releases an eager send
+      drop->s->consumed = true;
+      drop->s->pair.reset();
+    }
+  }
+
+  void notify() { cv_.notify_all(); }
+  std::mutex& mutex() { return mu_; }  // the eager slab is handed out under the mailbox lock
+
+  // counts of unmatched requests (tests)
+  size_t pending() {
+    std::lock_guard<std::mutex> g(mu_);
+    size_t n = 0;
+    for (auto& l : recvs_) n += l.size();
+    for (auto& l : sends_) n += l.size();
+    return n;
+  }
+
+ private:
+  // The checks at match time (mu_ held); false for a pair that is FAILED
+  bool check(P2PPair& p) {
+    const P2PReq &s = *p.s, &r = *p.r;
+    auto bad = [&](const std::string& why) {
+      p.state = kPairFailed;
+      p.err = kP2PErrArg;
+      p.msg = why + ": " + s.envelope() + " matched " + r.envelope();
+    };
+    if (s.bytes > 0 && s.base != r.base) {
+      bad("base type " + std::to_string(s.base) + " sent, base type " + std::to_string(r.base) + " received");
+      return false;
+    }
+    if (s.bytes > r.bytes) {
+      bad("the message of " + std::to_string(s.bytes) + " packed bytes is longer than the receive layout of " +
+          std::to_string(r.bytes));
+      return false;
+    }
+    if (s.rank == r.rank && s.bytes > 0) {
+      int a = 0, b = 0;
+      const OverlapResult o = strided_overlap({s.lay}, {r.lay}, &a, &b);
+      if (o == kSendRecvOverlap || o == kRecvOverlap) {
+        bad("a self-message whose send and receive layouts share a byte");
+        return false;
+      }
+    }
+    return true;
+  }
+
+  std::mutex mu_;
+  std::condition_variable cv_;
+  std::vector<std::deque<std::shared_ptr<P2PReq>>> recvs_, sends_;
+  std::deque<std::shared_ptr<P2PPair>> matched_;
+  int P_;
+};
+
+// ---- the eager slab -------------------------------------------------------------------------------------------
+
+// First-fit allocator over `cap` bytes in chunks aligned to 256 B. A chunk carries the request of the message
+// packed into it and is released once `done(request)` says its message has been moved, checked at the next
+// allocation. Not thread-safe: its rank calls it under the mailbox lock.
+class EagerSlab {
+ public:
+  static constexpr int64_t kAlign = 256;
+  explicit EagerSlab(int64_t cap = 0) : cap_(cap) {}
+  int64_t capacity() const { return cap_; }
+  size_t live() const { return chunks_.size(); }
+  // The offset of a chunk of `bytes` (> 0) for `owner`, or -1 when no gap is large enough
+  template <class Done>
+  int64_t alloc(int64_t bytes, const std::shared_ptr<P2PReq>& owner, Done done) {
+    for (auto it = chunks_.begin(); it != chunks_.end();) it = done(it->owner) ? chunks_.erase(it) : it + 1;
+    const int64_t need = (bytes + kAlign - 1) / kAlign * kAlign;
+    int64_t at = 0;
+    auto it = chunks_.begin();
+    for (; it != chunks_.end(); ++it) {  // sorted by offset
+      if (it->off - at >= need) break;
+      at = it->off + it->len;
+    }
+    if (it == chunks_.end() && cap_ - at < need) return -1;
+    chunks_.insert(it, Chunk{at, need, owner});
+    return at;
+  }
+  // Drops every chunk, handing its owner to f first
+  template <class F>
+  void clear(F f) {
+    for (Chunk& c : chunks_) f(c.owner);
+    chunks_.clear();
+  }
+
+ private:
+  struct Chunk {
+    int64_t off, len;
+    std::shared_ptr<P2PReq> owner;
+  };
+  std::vector<Chunk> chunks_;
+  int64_t cap_;
+};
+
+}  // namespace mpjx

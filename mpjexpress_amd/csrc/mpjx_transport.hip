@@ -470,6 +470,7 @@ extern "C" int mpjx_comm_init_smp(mpjx_comm_t* comms, int nranks, const int* dev
   w->idle.assign(nranks, 0);
   w->synced.assign(nranks, 0);
   w->direct = true;
+  w->mail = p2p_make_mailbox(nranks);
   w->single = std::all_of(devices, devices + nranks, [&](int d) { return d == devices[0]; });
   w->ready.assign(nranks, nullptr);
   w->done.assign(nranks, nullptr);
@@ -559,6 +560,7 @@ extern "C" int mpjx_comm_destroy(mpjx_comm_t c) {
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->last_stream) (void)hipStreamSynchronize(c->last_stream);
+  p2p_comm_destroy(c);
   c->tr.reset();
   for (void* p : c->retired) (void)hipFree(p);
   if (c->scratch) (void)hipFree(c->scratch);

@@ -13,6 +13,11 @@ reference's own programs (e.g. test/mpi/ccl/allreduce.java):
     comm.Allgather / Allgatherv / Gatherv / Scatterv / Alltoall / Alltoallv(sendbuf, sendoffset, sendcount[s],
         [sdispls,] sendtype, recvbuf, recvoffset, recvcount[s], [rdispls,] recvtype[, root])
                                                  src/mpi/Intracomm.java:363-690 (device tensors only)
+    comm.Send / Recv / Isend / Irecv(buf, offset, count, datatype, dest | source, tag), comm.Sendrecv(sendbuf,
+        sendoffset, sendcount, sendtype, dest, sendtag, recvbuf, recvoffset, recvcount, recvtype, source, recvtag),
+        comm.Sendrecv_replace(buf, offset, count, datatype, dest, sendtag, source, recvtag); Request.Wait / Test /
+        Is_null / Free / Waitall; Status.source / tag / Get_count / Get_elements
+                                                 src/mpi/Comm.java:381-2460, Request.java, Status.java (device tensors)
     comm.Pack_size(incount, datatype), comm.Pack(inbuf, offset, incount, datatype, outbuf, position),
     comm.Unpack(inbuf, position, outbuf, offset, outcount, datatype)     src/mpi/Comm.java:1860-1983
         (one mpjbuf section; the mpjbuf.Buffer is a torch.uint8 image on the device or in pinned memory)
@@ -199,6 +204,11 @@ class MPI:
     MAXLOC = Op(11, "MAXLOC")
     MINLOC = Op(12, "MINLOC")
 
+    ANY_SOURCE = -2  # src/mpi/MPI.java:132-136
+    ANY_TAG = -2
+    PROC_NULL = -3
+    UNDEFINED = -1
+
     isOldSelected = False  # conf mpjexpress.mpi.old.collectives
     COMM_WORLD = None
 
@@ -270,6 +280,74 @@ def _host_ptr(buf, off, dt, need):
     if off < 0 or off + need * dt.size > nbase:
         raise MPIException(f"offset {off} + count {need} exceeds buffer length {nbase}")
     return buf.ctypes.data + off * dt.baseSize
+
+
+class Status:
+    """mpi.Status (src/mpi/Status.java): source and tag of the matched message, and its length."""
+
+    def __init__(self, st=None):
+        self.source = st.source if st is not None else MPI.PROC_NULL
+        self.tag = st.tag if st is not None else MPI.ANY_TAG
+        self.error = st.error if st is not None else 0
+        self._st = st if st is not None else _lib.Status(MPI.PROC_NULL, MPI.ANY_TAG, 0, 0, 0)
+
+    def _counts(self, datatype):
+        c, e = ctypes.c_int64(), ctypes.c_int64()
+        _wrap("mpjx_get_count", ctypes.byref(self._st), datatype.code, ctypes.byref(c), ctypes.byref(e))
+        return c.value, e.value
+
+    def Get_count(self, datatype):
+        """Received items of `datatype`, or MPI.UNDEFINED if the message is not a whole number of them."""
+        return self._counts(datatype)[0]
+
+    def Get_elements(self, datatype):
+        """Received base elements."""
+        return self._counts(datatype)[1]
+
+
+class Request:
+    """mpi.Request (src/mpi/Request.java). The buffer belongs to the operation until Wait or a successful Test."""
+
+    def __init__(self, comm, handle, buf):
+        self._comm, self._h, self._buf = comm, ctypes.c_void_p(handle), buf
+
+    def Is_null(self):
+        return not self._h
+
+    def Wait(self):
+        st = _lib.Status()
+        try:
+            _wrap("mpjx_wait", ctypes.byref(self._h), ctypes.byref(st))
+        finally:
+            self._h, self._buf = ctypes.c_void_p(None), None
+        return Status(st)
+
+    def Test(self):
+        """The Status if the operation is complete, else None. Never blocks."""
+        st, flag = _lib.Status(), ctypes.c_int()
+        _wrap("mpjx_test", ctypes.byref(self._h), ctypes.byref(flag), ctypes.byref(st))
+        if not flag.value:
+            return None
+        self._buf = None
+        return Status(st)
+
+    def Free(self):
+        _wrap("mpjx_request_free", ctypes.byref(self._h))
+        self._buf = None
+
+    @staticmethod
+    def Waitall(array_of_requests):
+        """Waits for every request (of one communicator); returns their Statuses in order."""
+        reqs = list(array_of_requests)
+        n = len(reqs)
+        hs = (ctypes.c_void_p * max(n, 1))(*[r._h.value for r in reqs])
+        sts = (_lib.Status * max(n, 1))()
+        try:
+            _wrap("mpjx_waitall", n, hs, sts)
+        finally:
+            for r in reqs:
+                r._h, r._buf = ctypes.c_void_p(None), None
+        return [Status(sts[i]) for i in range(n)]
 
 
 class Intracomm:
@@ -712,6 +790,64 @@ class Intracomm:
                     3: "the section passes the end of the image"}.get(code, "malformed section")
             raise MPIException(f"Unpack: {what} (status {code}) at position {position}")
         return pos.value
+
+    # -- point-to-point (src/mpi/Comm.java:381-2460) on device tensors: counts in items of the datatype, offsets
+    # in base elements. Multicore worlds (include/mpjx.h); host arrays are not routed.
+    def _p2p_ptr(self, name, buf, offset, count, datatype):
+        if buf is None and count == 0:
+            return None
+        if not _is_torch(buf):
+            raise MPIException(f"{name} is provided for device-resident buffers")
+        self._sync_in(buf)
+        return _dev_ptr_dt(buf, offset, datatype, count)
+
+    def Isend(self, buf, offset, count, datatype, dest, tag):
+        p = self._p2p_ptr("Isend", buf, offset, count, datatype)
+        h = ctypes.c_void_p()
+        _wrap("mpjx_isend", self._h, p, count, datatype.code, dest, tag, ctypes.byref(h))
+        return Request(self, h.value, buf)
+
+    def Irecv(self, buf, offset, count, datatype, source, tag):
+        p = self._p2p_ptr("Irecv", buf, offset, count, datatype)
+        h = ctypes.c_void_p()
+        _wrap("mpjx_irecv", self._h, p, count, datatype.code, source, tag, ctypes.byref(h))
+        return Request(self, h.value, buf)
+
+    def Send(self, buf, offset, count, datatype, dest, tag):
+        p = self._p2p_ptr("Send", buf, offset, count, datatype)
+        _wrap("mpjx_send", self._h, p, count, datatype.code, dest, tag)
+
+    def Recv(self, buf, offset, count, datatype, source, tag):
+        p = self._p2p_ptr("Recv", buf, offset, count, datatype)
+        st = _lib.Status()
+        _wrap("mpjx_recv", self._h, p, count, datatype.code, source, tag, ctypes.byref(st))
+        return Status(st)
+
+    def Sendrecv(self, sendbuf, sendoffset, sendcount, sendtype, dest, sendtag, recvbuf, recvoffset, recvcount,
+                 recvtype, source, recvtag):
+        sp = self._p2p_ptr("Sendrecv", sendbuf, sendoffset, sendcount, sendtype)
+        rp = self._p2p_ptr("Sendrecv", recvbuf, recvoffset, recvcount, recvtype)
+        st = _lib.Status()
+        _wrap("mpjx_sendrecv", self._h, sp, sendcount, sendtype.code, dest, sendtag, rp, recvcount, recvtype.code,
+              source, recvtag, ctypes.byref(st))
+        return Status(st)
+
+    def Sendrecv_replace(self, buf, offset, count, datatype, dest, sendtag, source, recvtag):
+        p = self._p2p_ptr("Sendrecv_replace", buf, offset, count, datatype)
+        st = _lib.Status()
+        _wrap("mpjx_sendrecv_replace", self._h, p, count, datatype.code, dest, sendtag, source, recvtag,
+              ctypes.byref(st))
+        return Status(st)
+
+    def set_p2p_timeout(self, seconds):
+        """This rank's limit on every point-to-point host wait (mpjx_comm_set_p2p_timeout)."""
+        _wrap("mpjx_comm_set_p2p_timeout", self._h, float(seconds))
+
+    def p2p_stats(self):
+        """(launches, messages moved, eager sends, messages per launch) of this rank (mpjx_comm_p2p_stats)."""
+        a, b, c, m = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int()
+        _wrap("mpjx_comm_p2p_stats", self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(m))
+        return a.value, b.value, c.value, m.value
 
     def Bcast(self, buf, offset, count, datatype, root):
         if not _is_torch(buf):
