@@ -613,14 +613,15 @@ int mpjx_unpack(mpjx_comm_t comm, const void *image, int64_t image_bytes, int64_
  * kernel family instead of k_msgs: a comparison switch.
  *
  * Provided for multicore worlds (mpjx_comm_init_smp, _smp_rank) whose ranks address each other's memory, P = 1
- * included; RCCL, IPC and other worlds return MPJX_ERR_UNSUPPORTED. Not provided: Probe, Bsend /
- * Ssend / Rsend, persistent requests, Waitany / Waitsome / Test*all, Cancel, host arrays, big-endian and faithful
- * modes, MPI.PACKED / OBJECT.
+ * included; RCCL, IPC and other worlds return MPJX_ERR_UNSUPPORTED. Not provided: Probe / Iprobe,
+ * Bsend / Ssend / Rsend and their _init forms, Waitany / Waitsome / Test*all, Cancel, host arrays, big-endian and
+ * faithful modes, MPI.PACKED / OBJECT. Persistent requests are provided: see below.
  *
  * mpjx_status.elements is the received base elements (for a receive type of size 0: the receive count);
  * mpjx_get_count follows Comm.java:1517-1531: *count = elements / size if that divides, else MPJX_UNDEFINED; for a
  * type of size 0, *count = status->elements and *elements = MPJX_UNDEFINED. A request handle is set to NULL on
- * completion or free. mpjx_comm_destroy fails the communicator's pending requests; it does not free under them.
+ * completion or free (a persistent one: on free only). mpjx_comm_destroy fails the communicator's pending
+ * requests; it does not free under them.
  * mpjx_comm_p2p_stats: for this rank since creation, the k_msgs plus k_transpose launches, the messages it
  * moved, its sends that went eager, and the messages per k_msgs launch. */
 enum { MPJX_ANY_SOURCE = -2, MPJX_ANY_TAG = -2, MPJX_PROC_NULL = -3, MPJX_UNDEFINED = -1 }; /* MPI.java:132-136 */
@@ -647,6 +648,55 @@ int mpjx_get_count(const mpjx_status *status, int type, int64_t *count, int64_t 
 int mpjx_comm_set_p2p_timeout(mpjx_comm_t comm, double seconds);
 int mpjx_comm_p2p_stats(mpjx_comm_t comm, int64_t *launches, int64_t *moved, int64_t *eager,
                         int *table_max);
+
+/* ---- persistent requests: Send_init, Recv_init, Start, Startall ---------------------------------------------------
+ * (src/mpi/Comm.java Send_init / Recv_init; src/mpi/Prequest.java:72-119 Start, Startall)
+ * mpjx_send_init / mpjx_recv_init run every check mpjx_isend / mpjx_irecv run before posting (type, count, rank,
+ * tag, device pointer, a receive layout that shares a byte with itself), once, and return an INACTIVE persistent
+ * request: nothing is posted and nothing is enqueued. MPJX_ANY_SOURCE, MPJX_ANY_TAG and MPJX_PROC_NULL are legal
+ * where they are for mpjx_irecv and mpjx_isend. A derived type is captured here; freeing it afterwards does not
+ * disturb the request. Each persistent request gets a serial number, unique in the process and never reused.
+ * A NULL request, a negative count and a negative tag are judged from the arguments alone, before the
+ * communicator is looked at (MPJX_ERR_ARG even with a NULL communicator); *request is NULL after any failure.
+ *
+ * mpjx_start activates the request: to the mailbox it is an mpjx_isend or mpjx_irecv posted now, matched afresh
+ * at every start, never eager. mpjx_start on an active request, a request of mpjx_isend / mpjx_irecv or a NULL
+ * handle is MPJX_ERR_ARG and posts nothing. mpjx_startall checks every handle first (persistent, inactive, of one
+ * communicator, none twice; NULL entries are skipped; on any error nothing is posted), then records at most one
+ * ready event for all of them and posts them under one acquisition of the mailbox lock, in array order: the
+ * order non-overtaking sees.
+ *
+ * mpjx_wait, mpjx_test and mpjx_waitall take persistent handles mixed with others. On completion — and on an
+ * error of the wait: a mismatch, a timeout — a persistent handle stays non-NULL and becomes inactive; the status
+ * of a receive is filled as any receive's. That of a persistent SEND is the empty status (and the error, if
+ * any): this differs from a request of mpjx_isend, whose status names the sender and the tag; it is what the
+ * reference's programs check ("only the receivers have status values"). A wait or test on an inactive persistent
+ * request returns at once with the empty status. mpjx_request_free frees the request and sets the handle to NULL;
+ * a pending activation is withdrawn, or, if matched, let go. mpjx_request_is_persistent reports both properties
+ * of a handle (0, 0 for NULL).
+ *
+ * A pair of two persistent requests has the same addresses, layouts and length at every start. The first time a
+ * communicator moves such a pair it goes the way of any pair, and its segment is then stored in a slot of a device
+ * pool the communicator owns (1024 slots, allocated at first use). A later batch ALL of whose pairs are in the
+ * pool goes out in one launch of k_msgs_pool per batch_max (512) pairs, its argument an index of slots instead of
+ * a table of table_max segments. Any other batch — one plain pair among them, an element transpose, a pair
+ * not stored because the pool is full — takes the path above, unchanged. Slots of freed requests are reused.
+ * Storing a segment happens after its batch is enqueued and never fails the exchange: without memory for the
+ * pool, or if the store cannot be launched, the pair stays unpooled.
+ * MPJX_P2P_POOL=0 (read once per world) keeps every batch on that path: a comparison switch; so does
+ * MPJX_P2P_BATCH=0. mpjx_comm_p2p_pool_stats: for this rank since creation, the k_msgs_pool launches (counted in
+ * mpjx_comm_p2p_stats' launches too), the segments stored, the pairs moved from the pool, the slots in use now,
+ * and the pairs per launch. The three counters are atomic and may be read from any thread, also while the rank's
+ * own thread is inside a wait; slots_in_use may be asked for by the rank's own thread only. */
+int mpjx_send_init(mpjx_comm_t comm, const void *buf, int64_t count, int type, int dest, int tag,
+                   mpjx_request_t *request);
+int mpjx_recv_init(mpjx_comm_t comm, void *buf, int64_t count, int type, int source, int tag,
+                   mpjx_request_t *request);
+int mpjx_start(mpjx_request_t *request);
+int mpjx_startall(int n, mpjx_request_t *requests);
+int mpjx_request_is_persistent(mpjx_request_t request, int *persistent, int *active);
+int mpjx_comm_p2p_pool_stats(mpjx_comm_t comm, int64_t *pool_launches, int64_t *puts, int64_t *hits,
+                             int64_t *slots_in_use, int *batch_max);
 
 /* ---- host-resident variants (Java heap arrays / mpjbuf payloads) ---------------------------------
  * Synchronous. Buffers are ordinary host memory; the library stages them through device memory.

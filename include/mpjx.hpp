@@ -214,20 +214,44 @@ class Request {
   void Free() {
     if (r_) mpjx_request_free(&r_);
   }
-  static std::vector<Status> Waitall(std::vector<Request>& reqs) {
+  // R: Request or Prequest. A Request is null afterwards; a Prequest stays, inactive.
+  template <class R>
+  static std::vector<Status> Waitall(std::vector<R>& reqs) {
     std::vector<mpjx_request_t> h;
     for (Request& r : reqs) h.push_back(r.r_);
     std::vector<mpjx_status> st(reqs.size() + 1);
     const int rc = mpjx_waitall((int)h.size(), h.data(), st.data());
-    for (Request& r : reqs) r.r_ = nullptr;
+    for (size_t i = 0; i < reqs.size(); i++) static_cast<Request&>(reqs[i]).r_ = h[i];
     check(rc, "Waitall");
     std::vector<Status> out;
     for (size_t i = 0; i < reqs.size(); i++) out.emplace_back(st[i]);
     return out;
   }
 
- private:
+ protected:
   mpjx_request_t r_ = nullptr;
+};
+
+// mpi.Prequest (src/mpi/Prequest.java): a persistent request, made once by Intracomm::Send_init / Recv_init and
+// activated by Start or Startall. Wait, Test and Waitall complete the activation and leave it non-null and
+// inactive; Free() or the destructor releases it.
+class Prequest : public Request {
+ public:
+  Prequest() = default;
+  explicit Prequest(mpjx_request_t r) : Request(r) {}
+  Prequest(Prequest&&) noexcept = default;
+  Prequest& operator=(Prequest&&) noexcept = default;
+  void Start() { check(mpjx_start(&r_), "Start"); }
+  bool Is_active() const {
+    int a = 0;
+    check(mpjx_request_is_persistent(r_, nullptr, &a), "mpjx_request_is_persistent");
+    return a != 0;
+  }
+  static void Startall(std::vector<Prequest>& reqs) {
+    std::vector<mpjx_request_t> h;
+    for (Prequest& r : reqs) h.push_back(r.r_);
+    check(mpjx_startall((int)h.size(), h.data()), "Startall");
+  }
 };
 
 // One rank's communicator (src/mpi/Intracomm.java). Not copyable; Free() or the destructor releases it.
@@ -272,6 +296,20 @@ class Intracomm {
     mpjx_request_t r = nullptr;
     check(mpjx_irecv(c_, buf ? buf + offset : nullptr, count, dt.code, source, tag, &r), "Irecv");
     return Request(r);
+  }
+  template <class T>
+  Prequest Send_init(const T* buf, int offset, int count, const Datatype& dt, int dest, int tag) {
+    size_ok<T>(dt);
+    mpjx_request_t r = nullptr;
+    check(mpjx_send_init(c_, buf ? buf + offset : nullptr, count, dt.code, dest, tag, &r), "Send_init");
+    return Prequest(r);
+  }
+  template <class T>
+  Prequest Recv_init(T* buf, int offset, int count, const Datatype& dt, int source, int tag) {
+    size_ok<T>(dt);
+    mpjx_request_t r = nullptr;
+    check(mpjx_recv_init(c_, buf ? buf + offset : nullptr, count, dt.code, source, tag, &r), "Recv_init");
+    return Prequest(r);
   }
   template <class T>
   void Send(const T* buf, int offset, int count, const Datatype& dt, int dest, int tag) {

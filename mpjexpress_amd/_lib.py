@@ -119,12 +119,18 @@ def _declare(L):
         "mpjx_waitall": ([c_int, ctypes.POINTER(vp), ctypes.POINTER(Status)], c_int),
         "mpjx_request_free": ([ctypes.POINTER(vp)], c_int),
         "mpjx_get_count": ([ctypes.POINTER(Status), c_int, pi64, pi64], c_int),
+        "mpjx_send_init": ([vp, vp, c_i64, c_int, c_int, c_int, ctypes.POINTER(vp)], c_int),
+        "mpjx_recv_init": ([vp, vp, c_i64, c_int, c_int, c_int, ctypes.POINTER(vp)], c_int),
+        "mpjx_start": ([ctypes.POINTER(vp)], c_int),
+        "mpjx_startall": ([c_int, ctypes.POINTER(vp)], c_int),
+        "mpjx_request_is_persistent": ([vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int)], c_int),
     }
     # Bound like the rest but listed apart (BOUND, not EXPORTS): tests/test_abi.py compares EXPORTS with the names
     # its pattern finds in the header, and that pattern knows no digits
     more = {
         "mpjx_comm_set_p2p_timeout": ([vp, ctypes.c_double], c_int),
         "mpjx_comm_p2p_stats": ([vp, pi64, pi64, pi64, ctypes.POINTER(c_int)], c_int),
+        "mpjx_comm_p2p_pool_stats": ([vp, pi64, pi64, pi64, pi64, ctypes.POINTER(c_int)], c_int),
     }
     for name, (args, res) in list(sig.items()) + list(more.items()):
         f = getattr(L, name)
@@ -134,7 +140,7 @@ def _declare(L):
 
 
 EXPORTS = None
-BOUND = None  # every function the table binds: EXPORTS and the two whose names carry a digit
+BOUND = None  # every function the table binds: EXPORTS and those whose names carry a digit
 
 
 def lib():

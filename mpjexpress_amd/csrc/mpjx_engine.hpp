@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "mpjx_kernels.hpp"
+#include "mpjx_msgs_pool_plan.hpp"
 #include "mpjx_p2p_plan.hpp"
 
 namespace mpjx {
@@ -323,6 +324,13 @@ struct mpjx_comm {
   char* p2p_slab = nullptr;
   mpjx::EagerSlab p2p_chunks;
   int64_t p2p_launches = 0, p2p_moved = 0, p2p_eager = 0;
+  // The segment pool of the persistent requests (mpjx_msgs_pool_plan.hpp): kPoolSlots segments of device memory,
+  // allocated at the first put and freed where p2p_slab is; the host map from a pair of serials to its slot; the
+  // counters of mpjx_comm_p2p_pool_stats, atomic because another thread may read them while this rank's thread
+  // is inside a wait (the map itself belongs to the rank's thread)
+  mpjx::MsgSeg* p2p_pool = nullptr;
+  mpjx::PoolMap p2p_pool_map;
+  std::atomic<int64_t> p2p_pool_launches{0}, p2p_pool_puts{0}, p2p_pool_hits{0};
   // false once the communicator is destroyed: what a request handle that outlives it looks at
   std::shared_ptr<std::atomic<bool>> p2p_alive = std::make_shared<std::atomic<bool>>(true);
 };

@@ -32,6 +32,7 @@
 #include "mpjx_ops.hpp"
 #include "mpjx_indexed_plan.hpp"
 #include "mpjx_msgs_plan.hpp"
+#include "mpjx_msgs_pool_plan.hpp"
 #include "mpjx_pack_plan.hpp"
 #include "mpjx_strided_plan.hpp"
 #include "mpjx_transpose_plan.hpp"
@@ -665,6 +666,13 @@ hipError_t launch_transpose(const std::vector<TransposeSeg>& segs, hipStream_t s
 // plan_msg_seg, irregular sides' device tables uploaded on `s` or earlier; kMsgsMax segments per launch, each
 // launch added to *launches.
 hipError_t launch_msgs(const std::vector<MsgSeg>& segs, hipStream_t s, int64_t* launches);
+
+// The same for a batch whose segments all lie in the device pool (mpjx_k_msgs_pool.hip): `refs` name the slots
+// and their tiles for the tile size `nt` selects; kPoolBatchMax segments per launch, each launch added to
+// *launches. launch_msgs_pool_put stores segments into slots of the pool, kPoolPutMax per launch.
+hipError_t launch_msgs_pool(const MsgSeg* pool, const std::vector<PoolRef>& refs, bool nt, hipStream_t s,
+                            int64_t* launches);
+hipError_t launch_msgs_pool_put(MsgSeg* pool, const std::vector<std::pair<MsgSeg, int>>& puts, hipStream_t s);
 
 // One mpjbuf section packed from (unpack: unpacked into) a buffer of any layout (mpjx_k_pack.hip): the descriptor
 // planned by plan_pack_seg, an irregular layout's device table uploaded on `s` or earlier. One launch.

@@ -14,6 +14,12 @@
 //   wait      sleeps on the mailbox's condition variable while a request is unmatched (nothing is enqueued on
 //             the GPU for it), bounded by MPJX_P2P_TIMEOUT_S / mpjx_comm_set_p2p_timeout and by the world's
 //             `failed` flag; ends with Transport::wait on the stream, as MPJX_FLAG_BLOCKING does.
+//   persistent  Send_init / Recv_init keep the checked request of plan_req (Persist, mpjx_p2p_plan.hpp); Start and
+//             Startall post a fresh copy of it (Startall: one stream query, one ready event, one lock acquisition
+//             for the whole list). A pair of two persistent requests has the same segment at every start: after
+//             its first move the segment is stored in the communicator's device pool (mpjx_msgs_pool_plan.hpp),
+//             and a batch ALL of whose pairs are pooled goes out through k_msgs_pool (mpjx_k_msgs_pool.hip), one
+//             launch per kPoolBatchMax pairs. MPJX_P2P_POOL=0 keeps every batch on the path above.
 // Supported worlds: multicore worlds whose ranks address each other's memory (SmpWorld::direct), P = 1
 // included. The several-device form has no machine to be run on and is unverified.
 #include "mpjx_internal.hpp"
@@ -35,7 +41,8 @@ int p2p_launch_families(mpjx_comm* c, hipStream_t s, const std::vector<std::pair
 }  // namespace mpjx
 
 struct mpjx_request {
-  std::shared_ptr<P2PReq> q;
+  std::shared_ptr<P2PReq> q;                   // the posted request of a plain handle (req_of)
+  std::shared_ptr<Persist> pr;                 // a persistent request (mpjx_send_init / mpjx_recv_init): q stays empty
   mpjx_comm* c = nullptr;
   std::shared_ptr<SmpWorld> w;                 // keeps the mailbox and the world's `failed` flag alive
   std::shared_ptr<std::atomic<bool>> alive;    // false once the communicator is destroyed: c dangles
@@ -148,8 +155,89 @@ mpjx_request* handle_of(mpjx_comm* c, SmpTransport* t, const std::shared_ptr<P2P
   return h;
 }
 
+int launch_error(hipError_t e) {
+  if (e == hipErrorNoBinaryForGpu || e == hipErrorInvalidDeviceFunction)
+    return fail(MPJX_ERR_NO_DEVICE, "no gfx950 kernel image for this device: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return fail(MPJX_ERR_HIP, "point-to-point launch: %s", hipGetErrorString(e));
+  return MPJX_SUCCESS;
+}
+
+// True for a pair of two persistent requests: its segment is the same at every start
+bool pooled_kind(const P2PPair& p) { return p.s->serial != 0 && p.r->serial != 0; }
+
+// The batch through k_msgs_pool if every pair that moves bytes has its segment in c's pool: one launch per
+// kPoolBatchMax pairs. *done = false (and nothing enqueued) otherwise.
+int move_pooled(mpjx_comm* c, hipStream_t s, const std::vector<std::shared_ptr<P2PPair>>& batch, bool* done) {
+  *done = false;
+  if (!c->p2p_pool) return MPJX_SUCCESS;
+  std::vector<const PoolMap::Entry*> hit;
+  int64_t total = 0;
+  for (const auto& p : batch) {
+    if (p->s->bytes <= 0) continue;
+    const PoolMap::Entry* e = pooled_kind(*p) ? c->p2p_pool_map.find(p->s->serial, p->r->serial) : nullptr;
+    if (!e) return MPJX_SUCCESS;
+    hit.push_back(e);
+    total += e->bytes;
+  }
+  if (hit.empty()) return MPJX_SUCCESS;
+  for (const auto& p : batch) {
+    if (p->s->bytes <= 0) continue;
+    for (const P2PReq* q : {p->s.get(), p->r.get()})
+      if (q->rank != c->rank && q->ready) HIPCHK(hipStreamWaitEvent(s, event_of(q->ready), 0));
+  }
+  const bool nt = total >= kStridedStreamBytes;
+  std::vector<PoolRef> refs;
+  refs.reserve(hit.size());
+  for (const PoolMap::Entry* e : hit) refs.push_back(PoolRef{e->slot, nt ? e->tiles_nt : e->tiles});
+  int64_t launches = 0;
+  CHK(launch_error(launch_msgs_pool(c->p2p_pool, refs, nt, s, &launches)));
+  c->p2p_launches += launches;
+  c->p2p_pool_launches += launches;
+  c->p2p_pool_hits += (int64_t)hit.size();
+  *done = true;
+  return MPJX_SUCCESS;
+}
+
+// Stores the segments of the batch's newly met pairs of persistent requests into free slots of c's pool. The
+// batch itself is enqueued already: a put that cannot be made (no memory for the pool, a failed launch) leaves
+// its pairs unpooled, on the table path, and is no error of the exchange.
+void pool_put(mpjx_comm* c, hipStream_t s, const std::vector<std::pair<const P2PPair*, MsgSeg>>& fresh) {
+  std::vector<std::pair<MsgSeg, int>> puts;
+  std::vector<const P2PPair*> put_pairs;
+  for (const auto& f : fresh) {
+    const P2PReq &a = *f.first->s, &b = *f.first->r;
+    if (c->p2p_pool_map.find(a.serial, b.serial)) continue;
+    if (!c->p2p_pool) {
+      if (!PoolMap::poolable(f.second)) continue;
+      if (hipMalloc((void**)&c->p2p_pool, sizeof(MsgSeg) * (size_t)kPoolSlots) != hipSuccess) {
+        (void)hipGetLastError();
+        c->p2p_pool = nullptr;
+        return;
+      }
+    }
+    const int slot = c->p2p_pool_map.put(a.serial, b.serial, f.second, a.freed, b.freed);
+    if (slot < 0) continue;
+    puts.emplace_back(f.second, slot);
+    put_pairs.push_back(f.first);
+  }
+  if (puts.empty()) return;
+  if (launch_msgs_pool_put(c->p2p_pool, puts, s) != hipSuccess) {
+    (void)hipGetLastError();
+    for (const P2PPair* p : put_pairs) c->p2p_pool_map.erase(p->s->serial, p->r->serial);  // never looked up unwritten
+    return;
+  }
+  c->p2p_pool_puts += (int64_t)puts.size();
+}
+
 // The batch's segments onto `s`: the peers' ready events first
 int move_batch(mpjx_comm* c, SmpTransport* t, hipStream_t s, const std::vector<std::shared_ptr<P2PPair>>& batch) {
+  const bool pool_on = t->w->mail->batch && t->w->mail->seg_pool;
+  if (pool_on) {
+    bool done = false;
+    CHK(move_pooled(c, s, batch, &done));
+    if (done) return MPJX_SUCCESS;
+  }
+  std::vector<std::pair<const P2PPair*, MsgSeg>> fresh;
   std::vector<MsgSeg> segs;
   std::vector<TransposeSeg> tps;
   std::vector<std::pair<SideBytes, SideBytes>> plain;
@@ -178,6 +266,7 @@ int move_batch(mpjx_comm* c, SmpTransport* t, hipStream_t s, const std::vector<s
     const int rc = plan_msg_seg(a, stab, b, dtab, &m, &err);
     if (rc != kTypeOk) return fail(rc, "%s", err.c_str());
     segs.push_back(m);
+    if (pool_on && pooled_kind(*p)) fresh.emplace_back(p.get(), m);
   }
   if (!batched) return p2p_launch_families(c, s, plain);
   hipError_t e = launch_msgs(segs, s, &c->p2p_launches);
@@ -185,9 +274,8 @@ int move_batch(mpjx_comm* c, SmpTransport* t, hipStream_t s, const std::vector<s
     e = launch_transpose(tps, s);
     c->p2p_launches += ((int64_t)tps.size() + kTransposeMax - 1) / kTransposeMax;
   }
-  if (e == hipErrorNoBinaryForGpu || e == hipErrorInvalidDeviceFunction)
-    return fail(MPJX_ERR_NO_DEVICE, "no gfx950 kernel image for this device: %s", hipGetErrorString(e));
-  if (e != hipSuccess) return fail(MPJX_ERR_HIP, "point-to-point launch: %s", hipGetErrorString(e));
+  CHK(launch_error(e));
+  if (!fresh.empty()) pool_put(c, s, fresh);
   return MPJX_SUCCESS;
 }
 
@@ -218,9 +306,15 @@ void fill(mpjx_status* out, const P2PStatus& st) {
   out->bytes = st.bytes;
 }
 
+// The handle is done with: a plain request is deleted and *r is NULL; a persistent one stays, inactive (its
+// activation is withdrawn if unmatched, its pair let go)
 void drop(mpjx_request_t* r) {
   mpjx_request* h = *r;
   if (!h) return;
+  if (h->pr) {
+    h->pr->finish(h->w ? h->w->mail.get() : nullptr);
+    return;
+  }
   if (h->w && h->w->mail) {
     h->w->mail->withdraw(h->q);
     h->w->mail->release(h->q);
@@ -229,18 +323,26 @@ void drop(mpjx_request_t* r) {
   *r = nullptr;
 }
 
+// The posted request behind a handle: a plain handle's own, a persistent one's current activation (none while
+// it is inactive). Persist::act is the only record of whether a persistent request is active.
+const std::shared_ptr<P2PReq>& req_of(const mpjx_request* h) { return h->pr ? h->pr->act : h->q; }
+
+// A NULL handle or an inactive persistent request: complete, with the empty status
+bool idle(const mpjx_request* h) { return !h || !req_of(h); }
+
 Mailbox::Clock::time_point deadline_of(mpjx_comm* c, SmpTransport* t) {
   const double sec = c->p2p_timeout_s > 0 ? c->p2p_timeout_s : t->w->mail->timeout_s;
   return Mailbox::Clock::now() + std::chrono::duration_cast<Mailbox::Clock::duration>(std::chrono::duration<double>(sec));
 }
 
-// Waits for n requests of one communicator (NULL handles are skipped). Every handle is NULL on return.
+// Waits for n requests of one communicator (NULL handles and inactive persistent requests are skipped). On
+// return every plain handle is NULL and every persistent one inactive.
 int wait_many(int n, mpjx_request_t* reqs, mpjx_status* statuses) {
   mpjx_comm* c = nullptr;
   for (int i = 0; i < n; i++) {
     if (statuses) fill(&statuses[i], P2PStatus{});
     mpjx_request* h = reqs[i];
-    if (!h) continue;
+    if (idle(h)) continue;
     if (!h->alive->load()) {
       for (int j = 0; j < n; j++) drop(&reqs[j]);
       return fail(MPJX_ERR_INTERNAL, "the request's communicator was destroyed while it was pending");
@@ -260,8 +362,8 @@ int wait_many(int n, mpjx_request_t* reqs, mpjx_status* statuses) {
   Mailbox& mb = *t->w->mail;
   const auto deadline = deadline_of(c, t);
   for (int i = 0; i < n && rc == MPJX_SUCCESS; i++) {
-    if (!reqs[i]) continue;
-    const std::shared_ptr<P2PReq>& q = reqs[i]->q;
+    if (idle(reqs[i])) continue;
+    const std::shared_ptr<P2PReq> q = req_of(reqs[i]);
     for (;;) {
       rc = progress(c, t, s);
       if (rc != MPJX_SUCCESS) break;
@@ -286,8 +388,8 @@ int wait_many(int n, mpjx_request_t* reqs, mpjx_status* statuses) {
   }
   // every request is settled: order the stream after the batches other ranks moved, then drain it
   for (int i = 0; i < n; i++) {
-    if (!reqs[i]) continue;
-    const std::shared_ptr<P2PPair> p = reqs[i]->q->pair;
+    if (idle(reqs[i])) continue;
+    const std::shared_ptr<P2PPair> p = req_of(reqs[i])->pair;
     if (p && p->state == kPairLaunched && p->mover != c->rank && p->done) {
       const hipError_t e = hipStreamWaitEvent(s, event_of(p->done), 0);
       if (e != hipSuccess && rc == MPJX_SUCCESS) rc = fail(MPJX_ERR_HIP, "hipStreamWaitEvent: %s", hipGetErrorString(e));
@@ -298,8 +400,8 @@ int wait_many(int n, mpjx_request_t* reqs, mpjx_status* statuses) {
   c->last_recorded = false;
   std::string first;
   for (int i = 0; i < n; i++) {
-    if (!reqs[i]) continue;
-    const std::shared_ptr<P2PReq>& q = reqs[i]->q;
+    if (idle(reqs[i])) continue;
+    const std::shared_ptr<P2PReq> q = req_of(reqs[i]);
     if (q->orphan && !q->pair && rc == MPJX_SUCCESS) {
       rc = MPJX_ERR_INTERNAL;
       first = "the request was withdrawn: " + q->envelope();
@@ -405,6 +507,8 @@ std::shared_ptr<Mailbox> p2p_make_mailbox(int P) {
   mb->pool_bytes = (int64_t)env_double("MPJX_P2P_EAGER_POOL_MIB", 8) << 20;
   const char* e = getenv("MPJX_P2P_BATCH");
   mb->batch = !(e && e[0] == '0' && e[1] == 0);
+  e = getenv("MPJX_P2P_POOL");
+  mb->seg_pool = !(e && e[0] == '0' && e[1] == 0);
   return mb;
 }
 
@@ -418,6 +522,8 @@ void p2p_comm_destroy(mpjx_comm* c) {
   }
   if (c->p2p_slab) (void)hipFree(c->p2p_slab);
   c->p2p_slab = nullptr;
+  if (c->p2p_pool) (void)hipFree(c->p2p_pool);
+  c->p2p_pool = nullptr;
 }
 
 }  // namespace mpjx
@@ -519,7 +625,7 @@ extern "C" int mpjx_test(mpjx_request_t* request, int* flag, mpjx_status* status
   *flag = 0;
   fill(status, P2PStatus{});
   mpjx_request* h = *request;
-  if (!h) {
+  if (idle(h)) {
     *flag = 1;
     return MPJX_SUCCESS;
   }
@@ -533,8 +639,9 @@ extern "C" int mpjx_test(mpjx_request_t* request, int* flag, mpjx_status* status
   CHK(p2p_world(c, &t));
   CHK(p2p_begin(c, &s));
   CHK(progress(c, t, s));
-  if (!t->w->mail->settled(h->q)) return MPJX_SUCCESS;
-  const std::shared_ptr<P2PPair> p = h->q->pair;
+  const std::shared_ptr<P2PReq> q = req_of(h);
+  if (!t->w->mail->settled(q)) return MPJX_SUCCESS;
+  const std::shared_ptr<P2PPair> p = q->pair;
   if (p && p->state == kPairLaunched && p->done) {
     const hipError_t e = hipEventQuery(event_of(p->done));
     if (e == hipErrorNotReady) {
@@ -543,7 +650,7 @@ extern "C" int mpjx_test(mpjx_request_t* request, int* flag, mpjx_status* status
     }
     if (e != hipSuccess) return fail(MPJX_ERR_HIP, "hipEventQuery: %s", hipGetErrorString(e));
   }
-  const P2PStatus st = p2p_status(*h->q);
+  const P2PStatus st = p2p_status(*q);
   const std::string msg = p ? p->msg : std::string();
   fill(status, st);
   *flag = 1;
@@ -553,7 +660,129 @@ extern "C" int mpjx_test(mpjx_request_t* request, int* flag, mpjx_status* status
 
 extern "C" int mpjx_request_free(mpjx_request_t* request) {
   if (!request) return fail(MPJX_ERR_ARG, "request is NULL");
+  if (*request && (*request)->pr) {  // Prequest.Free: a pending activation is withdrawn or orphaned, then the plan goes
+    mpjx_request* h = *request;
+    drop(request);
+    delete h;
+    *request = nullptr;
+    return MPJX_SUCCESS;
+  }
   drop(request);
+  return MPJX_SUCCESS;
+}
+
+// ---- persistent requests (src/mpi/Prequest.java; Comm.java Send_init / Recv_init) ---------------------------------
+
+namespace {
+
+// Send_init / Recv_init. What can be judged from the arguments alone is judged first (as mpjx_pack does), so a
+// NULL request, a negative count and a negative tag are MPJX_ERR_ARG whatever the communicator is, NULL included.
+int init_impl(mpjx_comm* c, bool send, const void* buf, int64_t count, int type, int peer, int tag,
+              mpjx_request_t* request) {
+  const char* who = send ? "mpjx_send_init" : "mpjx_recv_init";
+  if (!request) return fail(MPJX_ERR_ARG, "%s: request is NULL", who);
+  *request = nullptr;
+  if (count < 0) return fail(MPJX_ERR_ARG, "%s: negative count %lld", who, (long long)count);
+  if (tag < 0 && !(!send && tag == MPJX_ANY_TAG)) return fail(MPJX_ERR_ARG, "%s: tag %d is negative", who, tag);
+  COMM_ARG(c);
+  SmpTransport* t = nullptr;
+  CHK(p2p_world(c, &t));
+  std::shared_ptr<P2PReq> q;
+  CHK(plan_req(c, send, buf, count, type, peer, tag, &q));
+  mpjx_request* h = handle_of(c, t, nullptr);
+  h->pr = std::make_shared<Persist>(*q);
+  *request = h;
+  return MPJX_SUCCESS;
+}
+
+// The checks of Start on one handle; `what` names the call
+int startable(const mpjx_request* h, const char* what) {
+  if (!h) return fail(MPJX_ERR_ARG, "%s: the request is NULL", what);
+  if (!h->pr) return fail(MPJX_ERR_ARG, "%s: not a persistent request (it was made by Isend or Irecv)", what);
+  if (h->pr->act)
+    return fail(MPJX_ERR_ARG, "%s: the request is active: %s has not completed", what, h->pr->act->envelope().c_str());
+  if (!h->alive->load()) return fail(MPJX_ERR_INTERNAL, "%s: the request's communicator was destroyed", what);
+  return MPJX_SUCCESS;
+}
+
+// Activates the n checked handles of communicator c (NULL entries skipped): one p2p_begin, one stream query, at
+// most one ready event shared by all, one acquisition of the mailbox lock, array order
+int start_many(mpjx_comm* c, int n, mpjx_request_t* reqs) {
+  SmpTransport* t = nullptr;
+  hipStream_t s = nullptr;
+  CHK(p2p_world(c, &t));
+  CHK(p2p_begin(c, &s));
+  bool moves = false;
+  for (int i = 0; i < n && !moves; i++)
+    moves = reqs[i] && reqs[i]->pr->plan.peer != MPJX_PROC_NULL && reqs[i]->pr->plan.bytes > 0;
+  std::shared_ptr<void> ready;
+  if (moves && hipStreamQuery(s) != hipSuccess) {
+    (void)hipGetLastError();
+    CHK(record_event(s, &ready));
+  }
+  std::vector<std::shared_ptr<P2PReq>> acts;
+  acts.reserve((size_t)n);
+  for (int i = 0; i < n; i++) {
+    if (!reqs[i]) continue;
+    std::shared_ptr<P2PReq> q = reqs[i]->pr->start();
+    if (!q) {  // active after all (startable() rules it out): post what was started, so that no handle is left half done
+      t->w->mail->post_all(acts);
+      return fail(MPJX_ERR_INTERNAL, "mpjx_start: request %d became active while the list was being started", i);
+    }
+    if (q->peer != MPJX_PROC_NULL && q->bytes > 0) q->ready = ready;
+    acts.push_back(std::move(q));
+  }
+  t->w->mail->post_all(acts);
+  return MPJX_SUCCESS;
+}
+
+}  // namespace
+
+extern "C" int mpjx_send_init(mpjx_comm_t c, const void* buf, int64_t count, int type, int dest, int tag,
+                              mpjx_request_t* request) {
+  return init_impl(c, true, buf, count, type, dest, tag, request);
+}
+
+extern "C" int mpjx_recv_init(mpjx_comm_t c, void* buf, int64_t count, int type, int source, int tag,
+                              mpjx_request_t* request) {
+  return init_impl(c, false, buf, count, type, source, tag, request);
+}
+
+extern "C" int mpjx_start(mpjx_request_t* request) {
+  if (!request) return fail(MPJX_ERR_ARG, "mpjx_start: request is NULL");
+  CHK(startable(*request, "mpjx_start"));
+  return start_many((*request)->c, 1, request);
+}
+
+extern "C" int mpjx_startall(int n, mpjx_request_t* requests) {
+  if (n < 0 || (n > 0 && !requests)) return fail(MPJX_ERR_ARG, "bad request list (n = %d)", n);
+  mpjx_comm* c = nullptr;
+  for (int i = 0; i < n; i++) {
+    if (!requests[i]) continue;
+    CHK(startable(requests[i], "mpjx_startall"));
+    if (c && requests[i]->c != c) return fail(MPJX_ERR_ARG, "the requests of one mpjx_startall must belong to one communicator");
+    c = requests[i]->c;
+    for (int j = 0; j < i; j++)
+      if (requests[j] == requests[i]) return fail(MPJX_ERR_ARG, "mpjx_startall: request %d appears twice in the list", i);
+  }
+  return c ? start_many(c, n, requests) : MPJX_SUCCESS;
+}
+
+extern "C" int mpjx_request_is_persistent(mpjx_request_t request, int* persistent, int* active) {
+  if (persistent) *persistent = request && request->pr ? 1 : 0;
+  if (active) *active = request && request->pr && request->pr->act ? 1 : 0;
+  return MPJX_SUCCESS;
+}
+
+extern "C" int mpjx_comm_p2p_pool_stats(mpjx_comm_t c, int64_t* pool_launches, int64_t* puts, int64_t* hits,
+                                        int64_t* slots_in_use, int* batch_max) {
+  SmpTransport* t = nullptr;
+  CHK(p2p_world(c, &t, false));
+  if (pool_launches) *pool_launches = c->p2p_pool_launches;
+  if (puts) *puts = c->p2p_pool_puts;
+  if (hits) *hits = c->p2p_pool_hits;
+  if (slots_in_use) *slots_in_use = c->p2p_pool_map.in_use();
+  if (batch_max) *batch_max = kPoolBatchMax;
   return MPJX_SUCCESS;
 }
 

@@ -57,6 +57,10 @@ struct P2PReq {
   bool orphan = false;     // its communicator was destroyed, or its wait gave up: no longer in any list
   bool eager = false;      // an eager send: its message lies in the sender's slab and nobody waits for it
   bool consumed = false;   // eager: the receiver has completed its wait, the slab chunk may be reused
+  // An activation of a persistent request (Persist below): the serial of the request behind it, and that
+  // request's `freed` flag. A plain request carries 0 and none.
+  uint64_t serial = 0;
+  std::shared_ptr<std::atomic<bool>> freed;
   std::string envelope() const {
     return std::string(send ? "send" : "recv") + "(rank " + std::to_string(rank) + (send ? " -> " : " <- ") +
            (peer == kAnySource ? std::string("ANY_SOURCE") : std::to_string(peer)) + ", tag " +
@@ -84,6 +88,7 @@ inline P2PStatus p2p_status(const P2PReq& q) {
   if (q.null_peer || !q.pair) return st;
   const P2PPair& p = *q.pair;
   st.error = p.err;
+  if (q.send && q.serial != 0) return st;  // Prequest: only the receivers have status values (the empty status)
   st.source = p.s->rank;
   st.tag = p.s->tag;
   if (p.err != kP2POk) return st;
@@ -111,11 +116,12 @@ class Mailbox {
   int size() const { return P_; }
 
   // Read once at world creation (mpjx_p2p.hip): MPJX_P2P_TIMEOUT_S, MPJX_P2P_EAGER_KIB, MPJX_P2P_EAGER_POOL_MIB,
-  // MPJX_P2P_BATCH
+  // MPJX_P2P_BATCH, MPJX_P2P_POOL
   double timeout_s = 300;
   int64_t eager_bytes = (int64_t)128 << 10;
   int64_t pool_bytes = (int64_t)8 << 20;
   bool batch = true;
+  bool seg_pool = true;  // MPJX_P2P_POOL: pairs of two persistent requests keep their segment on the device
 
   // Posts q (send: to q->peer; receive: at q->rank) and matches it if a partner waits. A PROC_NULL peer
   // completes at once. Returns the pair when one was made (FAILED pairs included).
@@ -123,33 +129,21 @@ class Mailbox {
     std::shared_ptr<P2PPair> made;
     {
       std::lock_guard<std::mutex> g(mu_);
-      if (q->peer == kProcNull) {
-        q->null_peer = true;
-        return nullptr;
-      }
-      const int dst = q->send ? q->peer : q->rank;
-      auto& mine = q->send ? sends_[(size_t)dst] : recvs_[(size_t)dst];
-      auto& other = q->send ? recvs_[(size_t)dst] : sends_[(size_t)dst];
-      for (auto it = other.begin(); it != other.end(); ++it) {
-        const P2PReq& s = q->send ? *q : **it;
-        const P2PReq& r = q->send ? **it : *q;
-        if ((r.peer == kAnySource || r.peer == s.rank) && (r.tag == kAnyTag || r.tag == s.tag)) {
-          made = std::make_shared<P2PPair>();
-          made->s = q->send ? q : *it;
-          made->r = q->send ? *it : q;
-          other.erase(it);
-          break;
-        }
-      }
-      if (!made) {
-        mine.push_back(q);
-        return nullptr;
-      }
-      made->s->pair = made;
-      made->r->pair = made;
-      if (check(*made)) matched_.push_back(made);
+      made = post_locked(q);
     }
-    cv_.notify_all();
+    if (made) cv_.notify_all();
+    return made;
+  }
+
+  // Posts every request of `qs` under ONE acquisition of the lock, in array order: the order non-overtaking
+  // sees (Prequest.Startall). Returns the pairs made.
+  size_t post_all(const std::vector<std::shared_ptr<P2PReq>>& qs) {
+    size_t made = 0;
+    {
+      std::lock_guard<std::mutex> g(mu_);
+      for (const auto& q : qs) made += post_locked(q) ? 1 : 0;
+    }
+    if (made) cv_.notify_all();
     return made;
   }
 
@@ -284,6 +278,37 @@ class Mailbox {
   }
 
  private:
+  // post's body (mu_ held)
+  std::shared_ptr<P2PPair> post_locked(const std::shared_ptr<P2PReq>& q) {
+    std::shared_ptr<P2PPair> made;
+    if (q->peer == kProcNull) {
+      q->null_peer = true;
+      return nullptr;
+    }
+    const int dst = q->send ? q->peer : q->rank;
+    auto& mine = q->send ? sends_[(size_t)dst] : recvs_[(size_t)dst];
+    auto& other = q->send ? recvs_[(size_t)dst] : sends_[(size_t)dst];
+    for (auto it = other.begin(); it != other.end(); ++it) {
+      const P2PReq& s = q->send ? *q : **it;
+      const P2PReq& r = q->send ? **it : *q;
+      if ((r.peer == kAnySource || r.peer == s.rank) && (r.tag == kAnyTag || r.tag == s.tag)) {
+        made = std::make_shared<P2PPair>();
+        made->s = q->send ? q : *it;
+        made->r = q->send ? *it : q;
+        other.erase(it);
+        break;
+      }
+    }
+    if (!made) {
+      mine.push_back(q);
+      return nullptr;
+    }
+    made->s->pair = made;
+    made->r->pair = made;
+    if (check(*made)) matched_.push_back(made);
+    return made;
+  }
+
   // The checks at match time (mu_ held); false for a pair that is FAILED
   bool check(P2PPair& p) {
     const P2PReq &s = *p.s, &r = *p.r;
@@ -317,6 +342,45 @@ class Mailbox {
   std::vector<std::deque<std::shared_ptr<P2PReq>>> recvs_, sends_;
   std::deque<std::shared_ptr<P2PPair>> matched_;
   int P_;
+};
+
+// ---- persistent requests (src/mpi/Prequest.java) ------------------------------------------------------------------
+
+// The checked plan of a send or a receive, made once by Send_init / Recv_init, and its current activation. Start
+// makes a fresh P2PReq from the plan, which the mailbox sees as an Isend or Irecv posted now; completion (or a
+// failed wait, or Free) makes the request inactive again. The serial is unique in the process and never reused:
+// it keys the device segment pool (mpjx_msgs_pool_plan.hpp). Not thread-safe: a request belongs to its rank's
+// thread, as every mpjx_request does.
+struct Persist {
+  P2PReq plan;                  // never posted itself: no pair, no ready event
+  std::shared_ptr<P2PReq> act;  // the pending activation; none while inactive
+
+  explicit Persist(const P2PReq& p) : plan(p) {
+    static std::atomic<uint64_t> next{1};
+    plan.serial = next.fetch_add(1, std::memory_order_relaxed);
+    plan.freed = std::make_shared<std::atomic<bool>>(false);
+    plan.pair.reset();
+    plan.ready.reset();
+  }
+  ~Persist() { plan.freed->store(true, std::memory_order_release); }
+  uint64_t serial() const { return plan.serial; }
+  bool active() const { return (bool)act; }
+  // The activation to post, or none if the request is active already
+  std::shared_ptr<P2PReq> start() {
+    if (act) return nullptr;
+    act = std::make_shared<P2PReq>(plan);
+    return act;
+  }
+  // The activation leaves the mailbox (unmatched: withdrawn; matched: its pair is let go) and the request is
+  // inactive. What a completed wait, a failed one and Free do.
+  void finish(Mailbox* mb) {
+    if (!act) return;
+    if (mb) {
+      mb->withdraw(act);
+      mb->release(act);
+    }
+    act.reset();
+  }
 };
 
 // ---- the eager slab -------------------------------------------------------------------------------------------

@@ -16,7 +16,9 @@ reference's own programs (e.g. test/mpi/ccl/allreduce.java):
     comm.Send / Recv / Isend / Irecv(buf, offset, count, datatype, dest | source, tag), comm.Sendrecv(sendbuf,
         sendoffset, sendcount, sendtype, dest, sendtag, recvbuf, recvoffset, recvcount, recvtype, source, recvtag),
         comm.Sendrecv_replace(buf, offset, count, datatype, dest, sendtag, source, recvtag); Request.Wait / Test /
-        Is_null / Free / Waitall; Status.source / tag / Get_count / Get_elements
+        Is_null / Free / Waitall; Status.source / tag / Get_count / Get_elements;
+        comm.Send_init / Recv_init(buf, offset, count, datatype, dest | source, tag) -> Prequest; Prequest.Start,
+        Prequest.Startall(list) (src/mpi/Prequest.java)
                                                  src/mpi/Comm.java:381-2460, Request.java, Status.java (device tensors)
     comm.Pack_size(incount, datatype), comm.Pack(inbuf, offset, incount, datatype, outbuf, position),
     comm.Unpack(inbuf, position, outbuf, offset, outcount, datatype)     src/mpi/Comm.java:1860-1983
@@ -346,8 +348,45 @@ class Request:
             _wrap("mpjx_waitall", n, hs, sts)
         finally:
             for r in reqs:
-                r._h, r._buf = ctypes.c_void_p(None), None
+                if not isinstance(r, Prequest):  # a persistent request stays, inactive
+                    r._h, r._buf = ctypes.c_void_p(None), None
         return [Status(sts[i]) for i in range(n)]
+
+
+class Prequest(Request):
+    """mpi.Prequest (src/mpi/Prequest.java): a persistent request, made once by Comm.Send_init / Recv_init and
+    activated by Start or Startall. Wait, Test and Waitall complete the activation and leave the request non-null
+    and inactive; the buffer belongs to the request until Free."""
+
+    def Start(self):
+        if self._comm is not None:
+            self._comm._sync_in(self._buf)  # what torch enqueued on the buffer precedes the message, as at Isend
+        _wrap("mpjx_start", ctypes.byref(self._h))
+
+    @staticmethod
+    def Startall(array_of_requests):
+        """Activates every request (of one communicator), in list order, in one call."""
+        reqs = list(array_of_requests)
+        n = len(reqs)
+        hs = (ctypes.c_void_p * max(n, 1))(*[r._h.value for r in reqs])
+        if reqs and reqs[0]._comm is not None:
+            reqs[0]._comm._sync_in(*[r._buf for r in reqs])  # one synchronize for the whole list
+        _wrap("mpjx_startall", n, hs)
+
+    def Wait(self):
+        st = _lib.Status()
+        _wrap("mpjx_wait", ctypes.byref(self._h), ctypes.byref(st))
+        return Status(st)
+
+    def Test(self):
+        st, flag = _lib.Status(), ctypes.c_int()
+        _wrap("mpjx_test", ctypes.byref(self._h), ctypes.byref(flag), ctypes.byref(st))
+        return Status(st) if flag.value else None
+
+    def Is_active(self):
+        p, a = ctypes.c_int(), ctypes.c_int()
+        _wrap("mpjx_request_is_persistent", self._h, ctypes.byref(p), ctypes.byref(a))
+        return bool(a.value)
 
 
 class Intracomm:
@@ -813,6 +852,20 @@ class Intracomm:
         _wrap("mpjx_irecv", self._h, p, count, datatype.code, source, tag, ctypes.byref(h))
         return Request(self, h.value, buf)
 
+    def Send_init(self, buf, offset, count, datatype, dest, tag):
+        """A persistent send (Comm.Send_init): checked now, posted by Prequest.Start / Startall."""
+        p = self._p2p_ptr("Send_init", buf, offset, count, datatype)
+        h = ctypes.c_void_p()
+        _wrap("mpjx_send_init", self._h, p, count, datatype.code, dest, tag, ctypes.byref(h))
+        return Prequest(self, h.value, buf)
+
+    def Recv_init(self, buf, offset, count, datatype, source, tag):
+        """A persistent receive (Comm.Recv_init)."""
+        p = self._p2p_ptr("Recv_init", buf, offset, count, datatype)
+        h = ctypes.c_void_p()
+        _wrap("mpjx_recv_init", self._h, p, count, datatype.code, source, tag, ctypes.byref(h))
+        return Prequest(self, h.value, buf)
+
     def Send(self, buf, offset, count, datatype, dest, tag):
         p = self._p2p_ptr("Send", buf, offset, count, datatype)
         _wrap("mpjx_send", self._h, p, count, datatype.code, dest, tag)
@@ -848,6 +901,14 @@ class Intracomm:
         a, b, c, m = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int()
         _wrap("mpjx_comm_p2p_stats", self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(m))
         return a.value, b.value, c.value, m.value
+
+    def p2p_pool_stats(self):
+        """(k_msgs_pool launches, segments stored, pairs moved from the pool, slots in use, pairs per launch) of
+        this rank (mpjx_comm_p2p_pool_stats)."""
+        a, b, c, d, m = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int()
+        _wrap("mpjx_comm_p2p_pool_stats", self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d),
+              ctypes.byref(m))
+        return a.value, b.value, c.value, d.value, m.value
 
     def Bcast(self, buf, offset, count, datatype, root):
         if not _is_torch(buf):
