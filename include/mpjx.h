@@ -74,6 +74,11 @@ enum {
  * point returns MPJX_ERR_ARG for them (an unknown datatype code). */
 enum { MPJX_LB = 10, MPJX_UB = 11 };
 
+/* MPI.PACKED (src/mpi/MPI.java:96, Datatype.java:67): an mpjbuf image, counted in BYTES. Valid only in the
+ * point-to-point calls named under "wire-format messages" below; mpjx_type_size(9) is 0 and every other entry
+ * point returns MPJX_ERR_ARG for it (an unknown datatype code). */
+enum { MPJX_PACKED = 9 };
+
 /* mpi.Op.opCode values (src/mpjdev/Constants.java:53-64; MPI.MAX..MPI.MINLOC at src/mpi/MPI.java:117-130) */
 enum {
   MPJX_MAX = 1, MPJX_MIN = 2, MPJX_SUM = 3, MPJX_PROD = 4, MPJX_LAND = 5,
@@ -613,9 +618,9 @@ int mpjx_unpack(mpjx_comm_t comm, const void *image, int64_t image_bytes, int64_
  * kernel family instead of k_msgs: a comparison switch.
  *
  * Provided for multicore worlds (mpjx_comm_init_smp, _smp_rank) whose ranks address each other's memory, P = 1
- * included; RCCL, IPC and other worlds return MPJX_ERR_UNSUPPORTED. Not provided: Probe / Iprobe,
- * Bsend / Ssend / Rsend and their _init forms, Waitany / Waitsome / Test*all, Cancel, host arrays, big-endian and
- * faithful modes, MPI.PACKED / OBJECT. Persistent requests are provided: see below.
+ * included; RCCL, IPC and other worlds return MPJX_ERR_UNSUPPORTED. Not provided: Bsend / Ssend / Rsend
+ * and their _init forms, Waitany / Waitsome / Test*all, Cancel, host arrays, big-endian and faithful modes,
+ * MPI.OBJECT. Persistent requests, MPI.PACKED messages and Probe / Iprobe are provided: see below.
  *
  * mpjx_status.elements is the received base elements (for a receive type of size 0: the receive count);
  * mpjx_get_count follows Comm.java:1517-1531: *count = elements / size if that divides, else MPJX_UNDEFINED; for a
@@ -697,6 +702,61 @@ int mpjx_startall(int n, mpjx_request_t *requests);
 int mpjx_request_is_persistent(mpjx_request_t request, int *persistent, int *active);
 int mpjx_comm_p2p_pool_stats(mpjx_comm_t comm, int64_t *pool_launches, int64_t *puts, int64_t *hits,
                              int64_t *slots_in_use, int *batch_max);
+
+/* ---- wire-format messages: MPI.PACKED, Probe, Iprobe ------------------------------------------------------------
+ * (src/mpi/Comm.java:391-437 send, :1446-1499 recv, :1761 Probe, :1811 Iprobe)
+ * In the reference every message is an mpjbuf image: a typed send packs one section and sends the image, a typed
+ * receive reads the first section's header and unpacks that many elements, and with MPI.PACKED either side hands
+ * over the image itself. MPJX_PACKED is accepted by mpjx_isend, mpjx_irecv, mpjx_send, mpjx_recv, mpjx_sendrecv,
+ * mpjx_sendrecv_replace, mpjx_send_init and mpjx_recv_init, and nowhere else. buf is then an mpjbuf image in device
+ * memory (the format: "Pack, Unpack, Pack_size" above) and count its length in BYTES: for a send the position
+ * mpjx_pack returned, for a receive the room. The image must be 8-byte aligned (MPJX_ERR_ARG at post, nothing is
+ * posted). The base-type test at match time passes when either side is PACKED:
+ *   PACKED -> PACKED   the image bytes move as a contiguous message; longer than the room is MPJX_ERR_ARG; 0 bytes is
+ *                      an empty message.
+ *   typed -> PACKED    the receiver's image gets ONE section at position 0: the 8 header bytes, then the send layout's
+ *                      elements in pack order, each base word big-endian: byte for byte what mpjx_pack(position 0)
+ *                      writes. 8 + payload above the room, or more than 2^31 - 1 base elements, completes both
+ *                      requests with MPJX_ERR_ARG at match and moves nothing. 0 items still write a header that
+ *                      announces 0. Bytes of the image past the section keep their contents.
+ *   PACKED -> typed    the first section of the sent image goes into the receive layout; later sections are ignored
+ *                      (the reference reads one header). An image of fewer than 8 bytes is MPJX_ERR_ARG at match. The
+ *                      KERNEL reads the header, since the image may have been written by a kernel a moment ago, and
+ *                      checks it before it loads any payload byte: a type code other than the receive base type's
+ *                      (MPJX_MPJBUF_BAD_TYPE), a negative count n or 8 + n * word bytes above the bytes sent
+ *                      (MPJX_MPJBUF_OVERRUN), n above the receive layout's base elements (MPJX_MPJBUF_BAD_COUNT). A
+ *                      bad header stores nothing into the receive buffer and completes the pair with MPJX_ERR_ARG on
+ *                      every party still waiting (mpjx_last_error names the code and both envelopes; the world stays
+ *                      usable; an eager mpjx_send that has returned has returned success). n below the room is legal:
+ *                      the first n packed elements of the layout are written, the rest keeps its contents.
+ * In a pair with a typed side, that side's buffer must be aligned to its base element (MPJX_ERR_ARG at match).
+ * Both on-the-fly kinds are moved by k_wire, one launch per table_max pairs of a claimed batch whatever their
+ * directions and layouts, counted in mpjx_comm_p2p_stats' launches too; such a pair is never stored in the segment
+ * pool of the persistent requests, and a batch that holds one takes the table path for its other pairs.
+ * Status of a receive: a typed receive of a PACKED message has elements = n and bytes = n * word bytes; a PACKED
+ * receive of a typed message has bytes = elements = 8 + payload; a PACKED receive of a PACKED message bytes =
+ * elements = the bytes sent. mpjx_get_count(status, MPJX_PACKED) treats the size as 1. Sender statuses keep their
+ * rule: the sender's own packed bytes. A blocking mpjx_send(PACKED) within the eager limit copies the image into
+ * the slab; a typed eager send that meets a PACKED receive is packed on the fly from the slab.
+ * mpjx_comm_p2p_wire_stats: for this rank since creation, the k_wire launches, the pairs it packed and unpacked on
+ * the fly, and the pairs per launch.
+ *
+ * mpjx_iprobe: *flag = 1 and *status filled if an unmatched send addressed to this rank, the first in post order,
+ * would match a receive (source, tag) posted now; wildcards are honoured, eager sends included. Nothing is consumed
+ * and nothing is enqueued on the GPU. mpjx_probe sleeps on the host until there is one, under the bound of every
+ * point-to-point wait (MPJX_P2P_TIMEOUT_S / mpjx_comm_set_p2p_timeout): on expiry MPJX_ERR_INTERNAL, and the world
+ * is marked failed. The status of a probed message: source, tag, bytes = the sender's packed bytes (image bytes for
+ * a PACKED send), elements = bytes / base element bytes, or MPJX_UNDEFINED when the sender used PACKED (the host
+ * cannot know the header). mpjx_wire_bytes gives the image a PACKED receive of that message needs: 8 + bytes, or
+ * bytes when elements is MPJX_UNDEFINED. A MPJX_PROC_NULL source returns at once with the empty status (flag 1).
+ *   MPJX_ERR_ARG: a NULL flag, a bad rank or tag, a NULL communicator, NULL arguments of mpjx_wire_bytes.
+ *   MPJX_ERR_UNSUPPORTED: RCCL, IPC and non-direct worlds; for the wait that moves it, a typed layout of 2^32 or
+ *   more granules in a pair with PACKED on the other side (as for one message of mpjx_alltoallv_dt). */
+int mpjx_iprobe(mpjx_comm_t comm, int source, int tag, int *flag, mpjx_status *status);
+int mpjx_probe(mpjx_comm_t comm, int source, int tag, mpjx_status *status);
+int mpjx_wire_bytes(const mpjx_status *status, int64_t *bytes);
+int mpjx_comm_p2p_wire_stats(mpjx_comm_t comm, int64_t *launches, int64_t *packed, int64_t *unpacked,
+                             int *table_max);
 
 /* ---- host-resident variants (Java heap arrays / mpjbuf payloads) ---------------------------------
  * Synchronous. Buffers are ordinary host memory; the library stages them through device memory.

@@ -153,6 +153,8 @@ struct MPI {
   static constexpr Datatype FLOAT2{MPJX_FLOAT2, 4, "FLOAT2", 2};
   static constexpr Datatype DOUBLE2{MPJX_DOUBLE2, 8, "DOUBLE2", 2};
   static constexpr Datatype LB{MPJX_LB, 0, "LB", 0}, UB{MPJX_UB, 0, "UB", 0};  // components of Datatype::Struct only
+  // an mpjbuf image, counted in bytes: the point-to-point calls only (include/mpjx.h "wire-format messages")
+  static constexpr Datatype PACKED{MPJX_PACKED, 1, "PACKED"};
   static constexpr Op MAX{MPJX_MAX, "MAX"}, MIN{MPJX_MIN, "MIN"}, SUM{MPJX_SUM, "SUM"},
       PROD{MPJX_PROD, "PROD"}, LAND{MPJX_LAND, "LAND"}, BAND{MPJX_BAND, "BAND"}, LOR{MPJX_LOR, "LOR"},
       BOR{MPJX_BOR, "BOR"}, LXOR{MPJX_LXOR, "LXOR"}, BXOR{MPJX_BXOR, "BXOR"}, MAXLOC{MPJX_MAXLOC, "MAXLOC"},
@@ -177,6 +179,12 @@ struct Status {
     int64_t e = 0;
     check(mpjx_get_count(&st, dt.code, nullptr, &e), "Get_elements");
     return (int)e;
+  }
+  // bytes of the image a Recv(MPI::PACKED) of the probed message needs (mpjx_wire_bytes)
+  int64_t wire_bytes() const {
+    int64_t n = 0;
+    check(mpjx_wire_bytes(&st, &n), "wire_bytes");
+    return n;
   }
 };
 
@@ -341,6 +349,20 @@ class Intracomm {
     mpjx_status st;
     check(mpjx_sendrecv_replace(c_, buf ? buf + offset : nullptr, count, dt.code, dest, sendtag, source, recvtag, &st),
           "Sendrecv_replace");
+    return Status(st);
+  }
+  // Comm.Iprobe: true and *status filled if a Recv(source, tag) posted now would take a message; nothing is consumed
+  bool Iprobe(int source, int tag, Status* status = nullptr) {
+    int flag = 0;
+    mpjx_status st;
+    check(mpjx_iprobe(c_, source, tag, &flag, &st), "Iprobe");
+    if (flag && status) *status = Status(st);
+    return flag != 0;
+  }
+  // Comm.Probe: waits on the host for such a message
+  Status Probe(int source, int tag) {
+    mpjx_status st;
+    check(mpjx_probe(c_, source, tag, &st), "Probe");
     return Status(st);
   }
   void SetP2PTimeout(double seconds) { check(mpjx_comm_set_p2p_timeout(c_, seconds), "mpjx_comm_set_p2p_timeout"); }

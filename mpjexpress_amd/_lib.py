@@ -124,6 +124,9 @@ def _declare(L):
         "mpjx_start": ([ctypes.POINTER(vp)], c_int),
         "mpjx_startall": ([c_int, ctypes.POINTER(vp)], c_int),
         "mpjx_request_is_persistent": ([vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int)], c_int),
+        "mpjx_iprobe": ([vp, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(Status)], c_int),
+        "mpjx_probe": ([vp, c_int, c_int, ctypes.POINTER(Status)], c_int),
+        "mpjx_wire_bytes": ([ctypes.POINTER(Status), pi64], c_int),
     }
     # Bound like the rest but listed apart (BOUND, not EXPORTS): tests/test_abi.py compares EXPORTS with the names
     # its pattern finds in the header, and that pattern knows no digits
@@ -131,6 +134,7 @@ def _declare(L):
         "mpjx_comm_set_p2p_timeout": ([vp, ctypes.c_double], c_int),
         "mpjx_comm_p2p_stats": ([vp, pi64, pi64, pi64, ctypes.POINTER(c_int)], c_int),
         "mpjx_comm_p2p_pool_stats": ([vp, pi64, pi64, pi64, pi64, ctypes.POINTER(c_int)], c_int),
+        "mpjx_comm_p2p_wire_stats": ([vp, pi64, pi64, pi64, ctypes.POINTER(c_int)], c_int),
     }
     for name, (args, res) in list(sig.items()) + list(more.items()):
         f = getattr(L, name)

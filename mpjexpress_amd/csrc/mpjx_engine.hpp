@@ -324,6 +324,10 @@ struct mpjx_comm {
   char* p2p_slab = nullptr;
   mpjx::EagerSlab p2p_chunks;
   int64_t p2p_launches = 0, p2p_moved = 0, p2p_eager = 0;
+  // the typed <-> MPI.PACKED pairs (k_wire): the counters of mpjx_comm_p2p_wire_stats, and the pinned pages of
+  // the unpack pairs' result slots (mpjx_p2p.hip: a page outlives the communicator while a pair holds a slot)
+  int64_t p2p_wire_launches = 0, p2p_wire_packed = 0, p2p_wire_unpacked = 0;
+  std::vector<std::shared_ptr<void>> p2p_wire_pages;
   // The segment pool of the persistent requests (mpjx_msgs_pool_plan.hpp): kPoolSlots segments of device memory,
   // allocated at the first put and freed where p2p_slab is; the host map from a pair of serials to its slot; the
   // counters of mpjx_comm_p2p_pool_stats, atomic because another thread may read them while this rank's thread

@@ -36,6 +36,7 @@
 #include "mpjx_pack_plan.hpp"
 #include "mpjx_strided_plan.hpp"
 #include "mpjx_transpose_plan.hpp"
+#include "mpjx_wire_plan.hpp"
 
 namespace mpjx {
 
@@ -677,6 +678,11 @@ hipError_t launch_msgs_pool_put(MsgSeg* pool, const std::vector<std::pair<MsgSeg
 // One mpjbuf section packed from (unpack: unpacked into) a buffer of any layout (mpjx_k_pack.hip): the descriptor
 // planned by plan_pack_seg, an irregular layout's device table uploaded on `s` or earlier. One launch.
 hipError_t launch_pack(const PackSeg& seg, bool unpack, hipStream_t s);
+
+// The typed <-> MPI.PACKED pairs of a point-to-point batch (mpjx_k_wire.hip): segments planned by plan_wire_pack /
+// plan_wire_unpack, irregular layouts' device tables uploaded on `s` or earlier; kWireMax segments per launch,
+// each launch added to *launches.
+hipError_t launch_wire(const std::vector<WireSeg>& segs, hipStream_t s, int64_t* launches);
 
 // IPC device sync (mpjx_ipc.hip): flag slots of the peers (peer[j] = peer j's slot for this rank),
 // this rank's own slots, and the bounded wait's limits; counter = a zeroed device word for the

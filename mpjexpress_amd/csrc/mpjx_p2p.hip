@@ -20,6 +20,11 @@
 //             its first move the segment is stored in the communicator's device pool (mpjx_msgs_pool_plan.hpp),
 //             and a batch ALL of whose pairs are pooled goes out through k_msgs_pool (mpjx_k_msgs_pool.hip), one
 //             launch per kPoolBatchMax pairs. MPJX_P2P_POOL=0 keeps every batch on the path above.
+//   wire      MPI.PACKED (base 9, an mpjbuf image counted in bytes) is taken by the eight calls that post. A pair
+//             with PACKED on exactly one side is packed or unpacked on the fly by k_wire (mpjx_k_wire.hip), one
+//             launch per kWireMax such pairs of a batch, beside the k_msgs launch for the rest; an unpack's header
+//             is checked on the device and its outcome {code, n} comes back through a pinned 8-byte slot that the
+//             first wait to see the batch complete reads (resolve_wire). Probe / Iprobe peek at the mailbox.
 // Supported worlds: multicore worlds whose ranks address each other's memory (SmpWorld::direct), P = 1
 // included. The several-device form has no machine to be run on and is unverified.
 #include "mpjx_internal.hpp"
@@ -103,8 +108,13 @@ int plan_req(mpjx_comm* c, bool send, const void* buf, int64_t count, int type, 
              std::shared_ptr<P2PReq>* out) {
   const char* who = send ? "send" : "receive";
   TypeForm f;
-  if (!type_form(type, &f)) return fail(MPJX_ERR_ARG, "%s: unknown or freed datatype code %d", who, type);
+  // MPI.PACKED: buf is an mpjbuf image, count its length (send) or room (receive) in bytes: a run of 1-byte words
+  const bool packed = type == MPJX_PACKED;
+  if (!(packed ? basic_form(MPJX_BYTE, &f) : type_form(type, &f)))
+    return fail(MPJX_ERR_ARG, "%s: unknown or freed datatype code %d", who, type);
   if (count < 0) return fail(MPJX_ERR_ARG, "%s: negative count %lld", who, (long long)count);
+  if (packed && (uintptr_t)buf % 8)
+    return fail(MPJX_ERR_ARG, "%s: image %p is not 8-byte aligned (the mpjbuf ALIGNMENT_UNIT)", who, buf);
   const bool wild = !send && peer == MPJX_ANY_SOURCE;
   if (!(peer >= 0 && peer < c->size) && peer != MPJX_PROC_NULL && !wild)
     return fail(MPJX_ERR_ARG, "%s: rank %d out of range (the communicator has %d)", who, peer, c->size);
@@ -118,7 +128,7 @@ int plan_req(mpjx_comm* c, bool send, const void* buf, int64_t count, int type, 
   q->rank = c->rank;
   q->peer = peer;
   q->tag = tag;
-  q->base = f.base;
+  q->base = packed ? kP2PPacked : f.base;
   q->bsz = f.bsz;
   q->bytes = q->lay.total();
   q->count = count;
@@ -173,6 +183,7 @@ int move_pooled(mpjx_comm* c, hipStream_t s, const std::vector<std::shared_ptr<P
   std::vector<const PoolMap::Entry*> hit;
   int64_t total = 0;
   for (const auto& p : batch) {
+    if (p->wire != kPairPlain) return MPJX_SUCCESS;  // never pooled: the batch takes the table path
     if (p->s->bytes <= 0) continue;
     const PoolMap::Entry* e = pooled_kind(*p) ? c->p2p_pool_map.find(p->s->serial, p->r->serial) : nullptr;
     if (!e) return MPJX_SUCCESS;
@@ -229,6 +240,55 @@ void pool_put(mpjx_comm* c, hipStream_t s, const std::vector<std::pair<const P2P
   c->p2p_pool_puts += (int64_t)puts.size();
 }
 
+// The result slots of the unpack pairs: 8-byte cells of pinned host memory, 512 to a page, which the kernel
+// stores with an ordinary store and the host reads without a copy. A slot lives as long as its pair, a page until
+// its communicator and its last slot are gone; taken on the mover's thread, given back on whichever drops the pair.
+struct WireSlotPage {
+  std::mutex mu;
+  uint64_t* cells = nullptr;
+  std::vector<int> free_cells;
+  static constexpr int kCells = 512;
+  ~WireSlotPage() {
+    if (cells) (void)hipHostFree(cells);
+  }
+};
+
+int wire_slot(mpjx_comm* c, std::shared_ptr<void>* out) {
+  std::shared_ptr<WireSlotPage> page;
+  int cell = -1;
+  for (const auto& v : c->p2p_wire_pages) {
+    auto pg = std::static_pointer_cast<WireSlotPage>(v);
+    std::lock_guard<std::mutex> g(pg->mu);
+    if (!pg->free_cells.empty()) {
+      cell = pg->free_cells.back();
+      pg->free_cells.pop_back();
+      page = pg;
+      break;
+    }
+  }
+  if (!page) {
+    page = std::make_shared<WireSlotPage>();
+    HIPCHK(hipHostMalloc((void**)&page->cells, sizeof(uint64_t) * WireSlotPage::kCells, hipHostMallocDefault));
+    for (int i = WireSlotPage::kCells - 1; i >= 1; i--) page->free_cells.push_back(i);
+    cell = 0;
+    c->p2p_wire_pages.push_back(page);
+  }
+  uint64_t* at = page->cells + cell;
+  *at = 0;
+  *out = std::shared_ptr<void>(at, [page, cell](void*) {
+    std::lock_guard<std::mutex> g(page->mu);
+    page->free_cells.push_back(cell);
+  });
+  return MPJX_SUCCESS;
+}
+
+// The outcome of an unpack pair whose batch has completed on the host's view: the slot's {code, n} into the pair
+void resolve_wire(Mailbox& mb, const std::shared_ptr<P2PPair>& p) {
+  if (!p || p->wire != kPairUnpack || p->state != kPairLaunched || !p->slot) return;
+  const volatile int32_t* v = static_cast<const volatile int32_t*>(p->slot.get());
+  mb.resolve(*p, v[0], v[1]);
+}
+
 // The batch's segments onto `s`: the peers' ready events first
 int move_batch(mpjx_comm* c, SmpTransport* t, hipStream_t s, const std::vector<std::shared_ptr<P2PPair>>& batch) {
   const bool pool_on = t->w->mail->batch && t->w->mail->seg_pool;
@@ -241,10 +301,37 @@ int move_batch(mpjx_comm* c, SmpTransport* t, hipStream_t s, const std::vector<s
   std::vector<MsgSeg> segs;
   std::vector<TransposeSeg> tps;
   std::vector<std::pair<SideBytes, SideBytes>> plain;
+  std::vector<WireSeg> wires;
+  int64_t packs = 0, unpacks = 0;
   const bool batched = t->w->mail->batch;
   const bool tr_on = p2p_transpose_on();
   std::string err;
   for (const auto& p : batch) {
+    if (p->wire != kPairPlain) {  // typed <-> PACKED: k_wire, under MPJX_P2P_BATCH=0 too (k_pack cannot take a short message)
+      for (const P2PReq* q : {p->s.get(), p->r.get()})
+        if (q->rank != c->rank && q->ready) HIPCHK(hipStreamWaitEvent(s, event_of(q->ready), 0));
+      const bool un = p->wire == kPairUnpack;
+      const P2PReq &typed = un ? *p->r : *p->s, &image = un ? *p->s : *p->r;
+      const IdxEnt* tab = nullptr;
+      if (typed.bytes > 0) CHK(p2p_idx_table(c, typed.lay, s, &tab));
+      // a pack's section has at most 2^31 - 1 words; a receive layout may be longer than any section
+      if (typed.bytes > 0 &&
+          (typed.bytes >> strided_granule_log(typed.lay, mpjx::packed_side(image.lay.base + 8, typed.bytes))) > kStridedMaxGran)
+        return fail(MPJX_ERR_UNSUPPORTED, "a layout of %lld bytes with MPI.PACKED on the other side exceeds 2^32 - 1 granules",
+                    (long long)typed.bytes);
+      WireSeg ws;
+      if (un) {
+        CHK(wire_slot(c, &p->slot));
+        plan_wire_unpack(typed.lay, tab, image.lay.base, image.bytes, typed.base, typed.bsz,
+                         (uint64_t)(uintptr_t)p->slot.get(), &ws);
+        unpacks++;
+      } else {
+        plan_wire_pack(typed.lay, tab, image.lay.base, typed.base, typed.bsz, &ws);
+        packs++;
+      }
+      wires.push_back(ws);
+      continue;
+    }
     if (p->s->bytes <= 0) continue;
     for (const P2PReq* q : {p->s.get(), p->r.get()})
       if (q->rank != c->rank && q->ready) HIPCHK(hipStreamWaitEvent(s, event_of(q->ready), 0));
@@ -267,6 +354,14 @@ int move_batch(mpjx_comm* c, SmpTransport* t, hipStream_t s, const std::vector<s
     if (rc != kTypeOk) return fail(rc, "%s", err.c_str());
     segs.push_back(m);
     if (pool_on && pooled_kind(*p)) fresh.emplace_back(p.get(), m);
+  }
+  if (!wires.empty()) {
+    int64_t n = 0;
+    CHK(launch_error(launch_wire(wires, s, &n)));
+    c->p2p_launches += n;
+    c->p2p_wire_launches += n;
+    c->p2p_wire_packed += packs;
+    c->p2p_wire_unpacked += unpacks;
   }
   if (!batched) return p2p_launch_families(c, s, plain);
   hipError_t e = launch_msgs(segs, s, &c->p2p_launches);
@@ -406,6 +501,7 @@ int wait_many(int n, mpjx_request_t* reqs, mpjx_status* statuses) {
       rc = MPJX_ERR_INTERNAL;
       first = "the request was withdrawn: " + q->envelope();
     }
+    if (rc == MPJX_SUCCESS) resolve_wire(mb, q->pair);  // the batch's completion event has passed
     const P2PStatus st = p2p_status(*q);
     if (statuses) fill(&statuses[i], st);
     if (st.error != kP2POk && rc == MPJX_SUCCESS) {
@@ -650,6 +746,7 @@ extern "C" int mpjx_test(mpjx_request_t* request, int* flag, mpjx_status* status
     }
     if (e != hipSuccess) return fail(MPJX_ERR_HIP, "hipEventQuery: %s", hipGetErrorString(e));
   }
+  resolve_wire(*t->w->mail, p);
   const P2PStatus st = p2p_status(*q);
   const std::string msg = p ? p->msg : std::string();
   fill(status, st);
@@ -789,7 +886,9 @@ extern "C" int mpjx_comm_p2p_pool_stats(mpjx_comm_t c, int64_t* pool_launches, i
 extern "C" int mpjx_get_count(const mpjx_status* status, int type, int64_t* count, int64_t* elements) {
   if (!status) return fail(MPJX_ERR_ARG, "status is NULL");
   TypeForm f;
-  if (!type_form(type, &f)) return fail(MPJX_ERR_ARG, "mpjx_get_count: unknown or freed datatype code %d", type);
+  // MPI.PACKED counts bytes: a type of size 1
+  if (!(type == MPJX_PACKED ? basic_form(MPJX_BYTE, &f) : type_form(type, &f)))
+    return fail(MPJX_ERR_ARG, "mpjx_get_count: unknown or freed datatype code %d", type);
   int64_t cn = 0, el = 0;
   p2p_get_count(status->elements, f.size(), &cn, &el);
   if (count) *count = cn;
@@ -812,5 +911,79 @@ extern "C" int mpjx_comm_p2p_stats(mpjx_comm_t c, int64_t* launches, int64_t* mo
   if (moved) *moved = c->p2p_moved;
   if (eager) *eager = c->p2p_eager;
   if (table_max) *table_max = kMsgsMax;
+  return MPJX_SUCCESS;
+}
+
+extern "C" int mpjx_comm_p2p_wire_stats(mpjx_comm_t c, int64_t* launches, int64_t* packed, int64_t* unpacked,
+                                        int* table_max) {
+  SmpTransport* t = nullptr;
+  CHK(p2p_world(c, &t, false));
+  if (launches) *launches = c->p2p_wire_launches;
+  if (packed) *packed = c->p2p_wire_packed;
+  if (unpacked) *unpacked = c->p2p_wire_unpacked;
+  if (table_max) *table_max = kWireMax;
+  return MPJX_SUCCESS;
+}
+
+// ---- Probe, Iprobe (src/mpi/Comm.java:1761, :1811) -----------------------------------------------------------------
+
+namespace {
+
+// Iprobe (block = false) and Probe. What can be judged from the arguments alone is judged first.
+int probe_impl(mpjx_comm* c, int source, int tag, int* flag, mpjx_status* status, bool block) {
+  const char* who = block ? "mpjx_probe" : "mpjx_iprobe";
+  if (!block && !flag) return fail(MPJX_ERR_ARG, "%s: flag is NULL", who);
+  if (flag) *flag = 0;
+  fill(status, P2PStatus{});
+  if (tag < 0 && tag != MPJX_ANY_TAG) return fail(MPJX_ERR_ARG, "%s: tag %d is negative", who, tag);
+  COMM_ARG(c);
+  SmpTransport* t = nullptr;
+  CHK(p2p_world(c, &t));
+  if (!(source >= 0 && source < c->size) && source != MPJX_PROC_NULL && source != MPJX_ANY_SOURCE)
+    return fail(MPJX_ERR_ARG, "%s: rank %d out of range (the communicator has %d)", who, source, c->size);
+  if (source == MPJX_PROC_NULL) {  // returns at once with the empty status
+    if (flag) *flag = 1;
+    return MPJX_SUCCESS;
+  }
+  Mailbox& mb = *t->w->mail;
+  P2PStatus st;
+  if (!block) {
+    if (mb.peek(c->rank, source, tag, &st)) {
+      *flag = 1;
+      fill(status, st);
+    }
+    return MPJX_SUCCESS;
+  }
+  // a host wait: nothing is enqueued on the GPU
+  const Mailbox::Wake w = mb.probe(c->rank, source, tag, deadline_of(c, t), &t->w->failed, &st);
+  if (w == Mailbox::kWakeMatched) {
+    fill(status, st);
+    return MPJX_SUCCESS;
+  }
+  if (w == Mailbox::kWakeFailed)
+    return fail(MPJX_ERR_INTERNAL, "multicore world: another rank failed while rank %d was probing", c->rank);
+  const std::string what = "rank " + std::to_string(c->rank) + " <- " +
+                           (source == MPJX_ANY_SOURCE ? std::string("ANY_SOURCE") : std::to_string(source)) + ", tag " +
+                           (tag == MPJX_ANY_TAG ? std::string("ANY_TAG") : std::to_string(tag));
+  c->tr->call_failed();  // every peer's wait and later call errors out: no rank hangs
+  mb.notify();
+  return fail(MPJX_ERR_INTERNAL, "point-to-point probe timed out: no message for (%s) within the limit", what.c_str());
+}
+
+}  // namespace
+
+extern "C" int mpjx_iprobe(mpjx_comm_t c, int source, int tag, int* flag, mpjx_status* status) {
+  return probe_impl(c, source, tag, flag, status, false);
+}
+
+extern "C" int mpjx_probe(mpjx_comm_t c, int source, int tag, mpjx_status* status) {
+  return probe_impl(c, source, tag, nullptr, status, true);
+}
+
+extern "C" int mpjx_wire_bytes(const mpjx_status* status, int64_t* bytes) {
+  if (!status || !bytes) return fail(MPJX_ERR_ARG, "mpjx_wire_bytes: NULL argument");
+  if (status->bytes < 0) return fail(MPJX_ERR_ARG, "mpjx_wire_bytes: negative bytes %lld", (long long)status->bytes);
+  // a typed message needs its section header; a PACKED one (elements unknown to the host) is an image already
+  *bytes = status->elements == MPJX_UNDEFINED ? status->bytes : 8 + status->bytes;
   return MPJX_SUCCESS;
 }

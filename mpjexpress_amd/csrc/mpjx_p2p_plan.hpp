@@ -13,7 +13,10 @@
 // A matched pair goes MATCHED -> CLAIMED -> LAUNCHED. Nothing is launched at post time: a call that waits
 // claims EVERY matched, unclaimed pair its rank is a party to (claim), moves the batch on its own stream and
 // marks it LAUNCHED with the batch's completion event (launched). Either party may move a pair, so no legal
-// order of waits deadlocks. A pair that fails its checks at match time (base types differ, the message is
+// order of waits deadlocks. The base-type test passes when either side is MPI.PACKED (kP2PPacked): such a pair is
+// marked for k_wire (PairWire) and checked for what the host can know of it. Mailbox::peek / probe are Probe and
+// Iprobe: they look at the unmatched sends and consume nothing.
+// A pair that fails its checks at match time (base types differ, the message is
 // longer than the receive layout, a self-message whose layouts share a byte) is FAILED at once on both
 // requests; nothing moves and the world stays usable.
 #pragma once
@@ -35,6 +38,10 @@ namespace mpjx {
 constexpr int kAnySource = -2, kAnyTag = -2, kProcNull = -3;  // src/mpi/MPI.java:132-136
 constexpr int kUndefined = -1;
 constexpr int kP2POk = 0, kP2PErrArg = -1, kP2PErrInternal = -7;  // MPJX_SUCCESS / _ERR_ARG / _ERR_INTERNAL
+constexpr int kP2PPacked = 9;  // MPI.PACKED's base type code: the request's buffer is an mpjbuf image, its word 1 byte
+// A pair with PACKED on exactly one side is moved by k_wire (mpjx_wire_plan.hpp): packed on the fly into the
+// receiver's image (typed -> PACKED) or unpacked on the fly from the sender's (PACKED -> typed)
+enum PairWire { kPairPlain = 0, kPairPack = 1, kPairUnpack = 2 };
 
 enum PairState { kPairMatched = 0, kPairClaimed = 1, kPairLaunched = 2, kPairFailed = 3 };
 
@@ -75,6 +82,12 @@ struct P2PPair {
   std::shared_ptr<void> done;   // the completion event of the batch that moved it (kept alive by the pair)
   int err = kP2POk;
   std::string msg;
+  int wire = kPairPlain;
+  // kPairUnpack: the 8-byte host-readable slot {int32 code, int32 n} the kernel stores, alive as long as the
+  // pair; `resolved` once a party has read it after the batch's completion event passed, n then in wire_n
+  std::shared_ptr<void> slot;
+  bool resolved = false;
+  int64_t wire_n = 0;
 };
 
 // What a completed request reports (mpjx_status)
@@ -94,6 +107,11 @@ inline P2PStatus p2p_status(const P2PReq& q) {
   if (p.err != kP2POk) return st;
   st.bytes = p.s->bytes;
   st.elements = p.s->bytes / (q.bsz > 0 ? q.bsz : 1);
+  if (!q.send && p.wire == kPairPack) st.bytes = st.elements = 8 + p.s->bytes;  // the section: header and payload
+  if (!q.send && p.wire == kPairUnpack) {  // what the header announced, from the slot
+    st.elements = p.wire_n;
+    st.bytes = p.wire_n * q.bsz;
+  }
   if (!q.send && q.empty_type) st.elements = q.count;  // Comm.java:1526-1531: a type of size 0 reports the count
   return st;
 }
@@ -127,11 +145,13 @@ class Mailbox {
   // completes at once. Returns the pair when one was made (FAILED pairs included).
   std::shared_ptr<P2PPair> post(const std::shared_ptr<P2PReq>& q) {
     std::shared_ptr<P2PPair> made;
+    bool wake;
     {
       std::lock_guard<std::mutex> g(mu_);
       made = post_locked(q);
+      wake = made || probers_ > 0;  // a probe sleeps for an unmatched send too
     }
-    if (made) cv_.notify_all();
+    if (wake) cv_.notify_all();
     return made;
   }
 
@@ -139,11 +159,13 @@ class Mailbox {
   // sees (Prequest.Startall). Returns the pairs made.
   size_t post_all(const std::vector<std::shared_ptr<P2PReq>>& qs) {
     size_t made = 0;
+    bool wake;
     {
       std::lock_guard<std::mutex> g(mu_);
       for (const auto& q : qs) made += post_locked(q) ? 1 : 0;
+      wake = made > 0 || probers_ > 0;
     }
-    if (made) cv_.notify_all();
+    if (wake) cv_.notify_all();
     return made;
   }
 
@@ -265,6 +287,49 @@ class Mailbox {
     }
   }
 
+  // Probe: the first unmatched send addressed to `rank`, in post order, that a receive (source, tag) posted now
+  // would match; wildcards honoured, eager sends included. Nothing is consumed. *st gets its source, tag, packed
+  // bytes (a PACKED send: image bytes) and elements (bytes / bsz, or kUndefined for a PACKED send, whose header
+  // the host cannot know).
+  bool peek(int rank, int source, int tag, P2PStatus* st) {
+    std::lock_guard<std::mutex> g(mu_);
+    return peek_locked(rank, source, tag, st);
+  }
+  // Sleeps until peek succeeds (kWakeMatched), until `deadline`, or until *failed is set, as wait does
+  Wake probe(int rank, int source, int tag, Clock::time_point deadline, const std::atomic<int>* failed, P2PStatus* st) {
+    std::unique_lock<std::mutex> lk(mu_);
+    struct Count {
+      int& n;
+      explicit Count(int& x) : n(x) { ++n; }
+      ~Count() { --n; }
+    } probing(probers_);
+    for (;;) {
+      if (peek_locked(rank, source, tag, st)) return kWakeMatched;
+      if (failed && failed->load(std::memory_order_acquire)) return kWakeFailed;
+      const auto now = Clock::now();
+      if (now >= deadline) return kWakeTimeout;
+      const auto slice = std::min<Clock::duration>(deadline - now, std::chrono::milliseconds(50));
+      cv_.wait_until(lk, std::chrono::system_clock::now() + slice);
+    }
+  }
+
+  // The result slot of an unpack pair was read after its batch's completion event passed: n base elements, or a
+  // nonzero MPJX_MPJBUF_* code, which completes the pair with MPJX_ERR_ARG on every party still waiting. The
+  // first call counts; both parties read the same slot.
+  void resolve(P2PPair& p, int code, int64_t n) {
+    std::lock_guard<std::mutex> g(mu_);
+    if (p.resolved) return;
+    p.resolved = true;
+    p.wire_n = code == 0 ? n : 0;
+    if (code != 0 && p.err == kP2POk) {
+      static const char* const names[] = {"", "MPJX_MPJBUF_BAD_TYPE", "MPJX_MPJBUF_BAD_COUNT", "MPJX_MPJBUF_OVERRUN"};
+      p.err = kP2PErrArg;
+      p.msg = std::string("the image's first section cannot be received (") + (code >= 1 && code <= 3 ? names[code] : "?") +
+              ", code " + std::to_string(code) + ", header count " + std::to_string(n) + "): " + p.s->envelope() +
+              " matched " + p.r->envelope();
+    }
+  }
+
   void notify() { cv_.notify_all(); }
   std::mutex& mutex() { return mu_; }  // the eager slab is handed out under the mailbox lock
 
@@ -317,11 +382,39 @@ class Mailbox {
       p.err = kP2PErrArg;
       p.msg = why + ": " + s.envelope() + " matched " + r.envelope();
     };
-    if (s.bytes > 0 && s.base != r.base) {
+    // The base-type test passes when either side is PACKED (Comm.java:394-407, :1460-1474)
+    const bool sp = s.base == kP2PPacked, rp = r.base == kP2PPacked;
+    if (sp != rp) {
+      const P2PReq& typed = sp ? r : s;
+      if (typed.bsz > 1 && typed.lay.base % (uint64_t)typed.bsz) {
+        bad("the typed buffer of a message with MPI.PACKED on the other side is not aligned to its " +
+            std::to_string(typed.bsz) + "-byte base element");
+        return false;
+      }
+      if (rp) {  // pack on the fly: one section at position 0 of the receiver's image
+        const int64_t words = s.bytes / (s.bsz > 0 ? s.bsz : 1);
+        if (words > 0x7fffffff) {
+          bad(std::to_string(words) + " base elements exceed the section header's int32 count (2^31 - 1)");
+          return false;
+        }
+        if (8 + s.bytes > r.bytes) {
+          bad("the section of 8 header and " + std::to_string(s.bytes) + " payload bytes is longer than the image of " +
+              std::to_string(r.bytes));
+          return false;
+        }
+        p.wire = kPairPack;
+      } else {  // unpack on the fly: the kernel reads the header; the host knows only the image's length
+        if (s.bytes < 8) {
+          bad("an image of " + std::to_string(s.bytes) + " bytes holds no section header");
+          return false;
+        }
+        p.wire = kPairUnpack;
+      }
+    } else if (s.bytes > 0 && s.base != r.base) {
       bad("base type " + std::to_string(s.base) + " sent, base type " + std::to_string(r.base) + " received");
       return false;
     }
-    if (s.bytes > r.bytes) {
+    if (p.wire == kPairPlain && s.bytes > r.bytes) {
       bad("the message of " + std::to_string(s.bytes) + " packed bytes is longer than the receive layout of " +
           std::to_string(r.bytes));
       return false;
@@ -337,6 +430,23 @@ class Mailbox {
     return true;
   }
 
+  // peek's body (mu_ held)
+  bool peek_locked(int rank, int source, int tag, P2PStatus* st) const {
+    for (const auto& sp : sends_[(size_t)rank]) {
+      const P2PReq& s = *sp;
+      if ((source == kAnySource || source == s.rank) && (tag == kAnyTag || tag == s.tag)) {
+        *st = P2PStatus{};
+        st->source = s.rank;
+        st->tag = s.tag;
+        st->bytes = s.bytes;
+        st->elements = s.base == kP2PPacked ? kUndefined : s.bytes / (s.bsz > 0 ? s.bsz : 1);
+        return true;
+      }
+    }
+    return false;
+  }
+
+  int probers_ = 0;  // calls asleep in probe (mu_ held): post then wakes them for an unmatched send as well
   std::mutex mu_;
   std::condition_variable cv_;
   std::vector<std::deque<std::shared_ptr<P2PReq>>> recvs_, sends_;

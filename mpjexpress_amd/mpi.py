@@ -190,6 +190,9 @@ class MPI:
     FLOAT2 = Datatype(7, "FLOAT2", np.float32, "float32", 2)
     DOUBLE2 = Datatype(8, "DOUBLE2", np.float64, "float64", 2)
 
+    # an mpjbuf image, counted in bytes: the point-to-point calls only (include/mpjx.h "wire-format messages")
+    PACKED = Datatype(9, "PACKED", np.uint8, "uint8")
+
     LB = Datatype(10, "LB", np.int8, "int8", 0)  # the bound markers: components of Datatype.Struct only
     UB = Datatype(11, "UB", np.int8, "int8", 0)
 
@@ -305,6 +308,12 @@ class Status:
     def Get_elements(self, datatype):
         """Received base elements."""
         return self._counts(datatype)[1]
+
+    def wire_bytes(self):
+        """Bytes of the image a Recv(MPI.PACKED) of the probed message needs (mpjx_wire_bytes)."""
+        n = ctypes.c_int64()
+        _wrap("mpjx_wire_bytes", ctypes.byref(self._st), ctypes.byref(n))
+        return n.value
 
 
 class Request:
@@ -838,6 +847,10 @@ class Intracomm:
         if not _is_torch(buf):
             raise MPIException(f"{name} is provided for device-resident buffers")
         self._sync_in(buf)
+        if datatype is MPI.PACKED:  # an image: a torch.uint8 tensor, offset and count in bytes
+            if buf.dtype != _lib.torch.uint8:
+                raise MPIException(f"{name}: an MPI.PACKED buffer must be a torch.uint8 tensor")
+            return _dev_ptr(buf, offset, datatype, count)
         return _dev_ptr_dt(buf, offset, datatype, count)
 
     def Isend(self, buf, offset, count, datatype, dest, tag):
@@ -891,6 +904,26 @@ class Intracomm:
         _wrap("mpjx_sendrecv_replace", self._h, p, count, datatype.code, dest, sendtag, source, recvtag,
               ctypes.byref(st))
         return Status(st)
+
+    def Iprobe(self, source, tag):
+        """The Status of the first unmatched message a Recv(source, tag) posted now would take, or None
+        (Comm.Iprobe). Nothing is consumed."""
+        flag, st = ctypes.c_int(), _lib.Status()
+        _wrap("mpjx_iprobe", self._h, source, tag, ctypes.byref(flag), ctypes.byref(st))
+        return Status(st) if flag.value else None
+
+    def Probe(self, source, tag):
+        """Waits on the host for such a message and returns its Status (Comm.Probe)."""
+        st = _lib.Status()
+        _wrap("mpjx_probe", self._h, source, tag, ctypes.byref(st))
+        return Status(st)
+
+    def p2p_wire_stats(self):
+        """(k_wire launches, pairs packed on the fly, pairs unpacked on the fly, pairs per launch) of this rank
+        (mpjx_comm_p2p_wire_stats)."""
+        a, b, c, m = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int()
+        _wrap("mpjx_comm_p2p_wire_stats", self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(m))
+        return a.value, b.value, c.value, m.value
 
     def set_p2p_timeout(self, seconds):
         """This rank's limit on every point-to-point host wait (mpjx_comm_set_p2p_timeout)."""
