@@ -1,12 +1,16 @@
 // CPU test of k_msgs' launch table and its two address mappings (mpjexpress_amd/csrc/mpjx_msgs_plan.hpp): plain
 // C++17, no HIP. Every packed byte of a segment is walked, lane by lane as the kernel does it, against
 // SideBytes::at. Built by the Makefile with g++, and by tests/test_p2p_abi.py under the sanitizers.
+// With --cases it plans the cases given on stdin instead and prints each one's cell (run_cases below;
+// tests/test_msgs_cases.py feeds it tests/msgs_cases.py).
 #include <stdio.h>
 #include <string.h>
 
+#include <iostream>
 #include <map>
 
 #include "../../mpjexpress_amd/csrc/mpjx_msgs_plan.hpp"
+#include "../../mpjexpress_amd/csrc/mpjx_transpose_plan.hpp"
 
 using namespace mpjx;
 
@@ -193,7 +197,84 @@ static void test_tables() {
   CHECK(kMsgsMax >= 8);  // a 2-D halo's eight messages fit one launch
 }
 
-int main() {
+// --cases: one case of tests/msgs_cases.py per line of stdin, the send side and then the receive side, each
+//   C | V <count> <blocklength> <stride> | I <n> <n blocklengths> <n displacements>
+//   <items> <byte offset of the buffer position>
+// over MPI.BYTE, planned over two 16-byte aligned buffers through plan_side and plan_msg_seg as the transport does.
+// Prints per case
+//   kind glog stab dtab ngran bytes sh da tiles tiles_nt transpose slo shi dlo dhi
+// (stab, dtab: the side has a block table; sh, da: (src - dst) & 15 and dst & 15, of a bytes segment; tiles at
+// kStridedTile and at kStridedTileNT; transpose: what plan_transpose_seg says; lo, hi: the bytes of its buffer
+// a layout touches). A message of up to 4 KiB is walked at both tiles, as above.
+static bool read_side(uint64_t buf, SideBytes* out) {
+  using V = std::vector<int64_t>;
+  char ctor;
+  long long v, n = 0;
+  if (!(std::cin >> ctor)) return false;
+  TypeForm b, f;
+  std::string err;
+  CHECK(basic_form(1, &b));
+  f = b;
+  if (ctor == 'V') {
+    long long a[3];
+    if (!(std::cin >> a[0] >> a[1] >> a[2])) return false;
+    CHECK(vector_form(a[0], a[1], a[2], b, &f, &err) == kTypeOk);
+  } else if (ctor == 'I') {
+    if (!(std::cin >> n) || n < 1 || n > (1 << 20)) return false;
+    V a;
+    for (long long i = 0; i < 2 * n && (std::cin >> v); i++) a.push_back(v);
+    if ((long long)a.size() != 2 * n) return false;
+    CHECK(indexed_form(n, a.data(), a.data() + n, b, &f, &err) == kTypeOk);
+    f.code = kDerivedBase + 1;
+  } else if (ctor != 'C') {
+    return false;
+  }
+  long long items, off;
+  if (!(std::cin >> items >> off) || items < 1 || off < 0) return false;
+  CHECK(plan_side(f, buf + (uint64_t)off, items, 0, out, &err));
+  return true;
+}
+
+static int run_cases() {
+  const uint64_t sbuf = 0x10000000, dbuf = 0x40000000;
+  int n = 0;
+  while (std::cin >> std::ws && std::cin.peek() != EOF) {
+    SideBytes s, d;
+    if (!read_side(sbuf, &s) || !read_side(dbuf, &d) || s.total() <= 0 || d.total() < s.total()) {
+      printf("case %d: malformed\n", n);
+      return 2;
+    }
+    MsgSeg m{};
+    std::string err;
+    const IdxEnt* st = s.irr ? s.irr->tab.data() : nullptr;
+    const IdxEnt* dt = d.irr ? d.irr->tab.data() : nullptr;
+    CHECK(plan_msg_seg(s, st, d, dt, &m, &err) == kTypeOk);
+    CHECK(m.bytes == s.total());
+    TransposeSeg ts;
+    const bool tr = plan_transpose_seg(s, d, &ts);
+    if (m.bytes <= 4096)
+      for (int64_t tile : {kStridedTile, kStridedTileNT}) check_msgs({{s, d}}, tile, 1);
+    uint64_t slo, shi, dlo, dhi;
+    s.span(&slo, &shi);
+    d.span(&dlo, &dhi);
+    const bool by = m.kind == kMsgBytes;
+    printf("%u %u %d %d %u %lld %u %u %lld %lld %d %lld %lld %lld %lld\n", m.kind, by ? 0u : m.g.glog,
+           !by && m.g.s.tab ? 1 : 0, !by && m.g.d.tab ? 1 : 0, by ? 0u : m.g.ngran, (long long)m.bytes,
+           by ? (unsigned)((m.g.s.r.base - m.g.d.r.base) & 15u) : 0u, by ? (unsigned)(m.g.d.r.base & 15u) : 0u,
+           (long long)msg_tiles(m, kStridedTile), (long long)msg_tiles(m, kStridedTileNT), tr ? 1 : 0,
+           (long long)(slo - sbuf), (long long)(shi - sbuf), (long long)(dlo - dbuf), (long long)(dhi - dbuf));
+    n++;
+  }
+  if (g_fail) {
+    printf("msgs_plan_test: %d FAILED\n", g_fail);
+    return 1;
+  }
+  printf("msgs_plan_test: ok (%d cases)\n", n);
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1 && std::string(argv[1]) == "--cases") return run_cases();
   test_bytes_kind();
   test_granule_kind();
   test_tables();
